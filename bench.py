@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: Gaussian-splats/sec, forward + backward, 1M Gaussians @ 1920x1080, SH degree 3.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1m_1080p_sh3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1m_1080p_sh3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it builds the synthetic inputs, ramps
+the clock, runs the W warm-up steps, times the K steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given (``DIR/<name>.npy``, see ``dump_outputs``) and prints the
+result line.  Everything else described below -- the per-stage breakdown pass, the work
+census, the dominant kernel's roofline and the CPU baselines -- runs only with ``--full``.
 
 One step = ``_C.rasterize_gaussians`` + ``_C.rasterize_gaussians_backward`` for one
 view, on synthetic inputs already resident in HBM.  When N > 1
@@ -16,7 +22,7 @@ object carries both timings and the pick.  Rank r renders view r (camera yawed b
 degrees), so per-GPU work is fixed as N grows ("weak" scaling) and value = N * P * K /
 (max over ranks of the K-step time).
 
-Rank 0 prints one JSON line.  It carries the roofline of the dominant kernel (its
+Rank 0 prints one JSON line.  With ``--full`` it carries the roofline of the dominant kernel (its
 algorithmic bytes per launch / its mean duration from HIP events on the launch
 stream), the host side of every step (``host``: forward call, the forward's wait for
 the instance count, backward enqueue, exchange), and the CPU baseline: the
@@ -269,6 +275,71 @@ class HostClock:
         return out
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per array: 4 MiB of float32, so a dump of a dozen arrays stays well under 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(directory: str, outputs: dict) -> dict:
+    """Write what the last timed step handed its caller as ``directory/<name>.npy``: float32 arrays
+    (float64 where the tensor is float64; integer outputs such as the radii as float32, exact below
+    2^24).  An output of more than DUMP_MAX_ELEMS elements is written as a fixed sample of that many of
+    its elements: the flattened array at the sorted indices ``default_rng(DUMP_SEED).integers(0, n,
+    DUMP_MAX_ELEMS)``, the same indices in every run and build, so two dumps compare element for element.
+    Returns {name: {"shape", "written", "sampled"}} for the result line."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    info = {}
+    for name, v in outputs.items():
+        if v is None:
+            continue
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        shape, sampled = list(a.shape), a.size > DUMP_MAX_ELEMS
+        if sampled:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_MAX_ELEMS))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": shape, "written": int(a.size), "sampled": bool(sampled)}
+    return info
+
+
+def headline(args, world, P, W, H, Kdeg, nr, elapsed, grouped, multi, ex, exchange):
+    """The keys every result line carries: the headline figure (value = world * P * steps / the timed
+    region's wall time, max over ranks), ms_per_step and the workload it was measured on."""
+    # BASELINE.json's metric names the headline workload; another --config says its own
+    metric = ("Gaussian-splats/sec fwd+bwd @1080p, 1M Gaussians" if args.config == "1m_1080p_sh3" else
+              f"Gaussian-splats/sec fwd+bwd @{W}x{H}, {P} Gaussians ({args.config}; not the headline metric)")
+    par = f"view-sharded x{world}"
+    if grouped:
+        # the backend that really ran (gloo in the one-GPU rehearsal, nccl = RCCL on ROCm)
+        be = "RCCL" if multi["backend"] == "nccl" else multi["backend"]
+        par += {"views": f" + {be} all-gather of " + ("sparse " if ex is not None and ex.sparse else "dense ")
+                + "view blocks",
+                "chunked": f" + {be} all-gathers of sparse view blocks in {args.exchange_chunks} Gaussian-range "
+                           "chunks, overlapped with the multi-view backward",
+                "allreduce": f" + {be} all-reduce of the gradient arena"}[exchange]
+    return {
+        "metric": metric,
+        "value": world * P * args.steps / elapsed,
+        "unit": "Gaussian-splats/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "clock_ramp_s": args.ramp_seconds,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic (frustum-uniform Gaussians, SURVEY.md 8d; seed 0)",
+        "config": {"workload": args.config, "gaussians": P, "width": W, "height": H, "sh_degree": Kdeg,
+                   "num_rendered": nr, "views": "one per GPU, yaw 5 deg x rank", "parallelism": par,
+                   "sh_layout": "dc + rest (separate_sh)" if args.separate_sh else "one [P,M,3] tensor"},
+        "full": bool(args.full),
+    }
+
+
 def _free_port() -> int:
     import socket
 
@@ -313,9 +384,17 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="1m_1080p_sh3", choices=sorted(syn.CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the per-stage breakdown pass, the work census, the dominant "
+                         "kernel's roofline (HIP events on every --roofline-every-th timed step) and, at N = 1, "
+                         "the CPU baselines; off by default, a plain run times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (image, inverse depth, radii, "
+                         "instance count, every gradient) as DIR/<name>.npy; large arrays as a fixed seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-census", action="store_true",
-                    help="skip the census pass (profiler runs: keeps its kernel instantiations out of the trace)")
+                    help="--full without the census pass (profiler runs: keeps its kernel instantiations out of "
+                         "the trace)")
     ap.add_argument("--exchange", choices=("auto", "views", "chunked", "dense", "allreduce"), default="auto",
                     help="N > 1: all-gather the sparse view blocks (views), the same in Gaussian-range chunks whose "
                          "all-gathers overlap the multi-view backward of the earlier chunks (chunked), the dense "
@@ -348,6 +427,9 @@ def main():
     args = parse_args(argv)
     if args.gpus < 1:
         print("[bench] error: --gpus must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("[bench] error: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         sys.exit(2)
     if not args.cpu_only:
         rc = maybe_launch(args, argv)
@@ -425,6 +507,7 @@ def main():
                                            "chunked" if args.exchange == "chunked" else "views")
     clock = HostClock()
     pc = time.perf_counter
+    last = {}
 
     def step(collective=True):
         t0 = pc()
@@ -444,8 +527,9 @@ def main():
             E.exchange(zero=arena.flat)  # the outputs zeroed beside the exchange; a live-list backward
             E.views_backward(scene.means3D, sh_dc, sh_rest, Kdeg, scene.opacities, scene.scales, scene.rotations,
                              1.0, out=arena.views())
+            grads = None  # the summed gradients are the arena's views
         else:
-            _C.rasterize_gaussians_backward(*bwd, out=arena.views())
+            grads = _C.rasterize_gaussians_backward(*bwd, out=arena.views())
             t3 = pc()
             if grouped and collective:
                 arena.all_reduce()
@@ -455,6 +539,8 @@ def main():
         clock.add("backward_call", t3 - t2)
         if grouped and collective:
             clock.add("exchange", t4 - t3)
+        if args.dump_outputs:  # what this step handed its caller (references only; written after the timed steps)
+            last.update(num_rendered=nr, color=color, invdepth=invd, radii=radii, grads=grads)
         return nr
 
     # Untimed clock ramp: the GPU lowers its clock when idle and takes ~0.1 s of load to come back
@@ -499,23 +585,24 @@ def main():
         for _ in range(2):
             step()
         torch.cuda.synchronize()
-    # Per-stage breakdown in a separate, untimed pass: every timed stage adds an event pair
-    # (~10 us of idle GPU each), so the timed region below records events only around the
-    # dominant kernel.
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-    torch.cuda.synchronize()
-    _lib.profile_enable(False)
-    stages = _lib.profile_collect()
-    per_stage = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in stages.items()}
-    dom = max(per_stage, key=per_stage.get)
-    # Work census (untimed, census kernel instantiations): how many (pixel, splat) pairs the render
-    # kernels blend -- their cost follows these pairs, not the per-instance bytes of the roofline.
-    census = None if args.no_census else _lib.census(lambda: step(collective=False), dev)
-
-    _lib.profile_reset()
+    per_stage, dom, census = {}, None, None
+    if args.full:
+        # Per-stage breakdown in a separate, untimed pass: every timed stage adds an event pair
+        # (~10 us of idle GPU each), so the timed region below records events only around the
+        # dominant kernel.
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+        torch.cuda.synchronize()
+        _lib.profile_enable(False)
+        stages = _lib.profile_collect()
+        per_stage = {k: (v[0] / v[1] if v[1] else 0.0) for k, v in stages.items()}
+        dom = max(per_stage, key=per_stage.get)
+        # Work census (untimed, census kernel instantiations): how many (pixel, splat) pairs the render
+        # kernels blend -- their cost follows these pairs, not the per-instance bytes of the roofline.
+        census = None if args.no_census else _lib.census(lambda: step(collective=False), dev)
+        _lib.profile_reset()
     every = max(1, args.roofline_every)
     if grouped:
         dist.barrier()
@@ -531,10 +618,10 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         ts = pc()
-        # the dominant kernel's launches are timed live, on its own stream, on every `every`-th step
-        if i % every == 0:
+        # --full: the dominant kernel's launches are timed live, on its own stream, on every `every`-th step
+        if dom is not None and i % every == 0:
             _lib.profile_enable(True, stages=[dom])
-        elif i % every == 1:
+        elif dom is not None and i % every == 1:
             _lib.profile_enable(False)
         nr = step()
         clock.add("step_wall", pc() - ts)
@@ -545,8 +632,19 @@ def main():
     clock.on = False
     _gc.callbacks.remove(_gc_cb)
     host = clock.summary(_lib.host_stats())
-    _lib.profile_enable(False)
-    dom_total, dom_calls = _lib.profile_collect()[dom]
+    if dom is not None:
+        _lib.profile_enable(False)
+        dom_total, dom_calls = _lib.profile_collect()[dom]
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's outputs: the forward's image, inverse depth, radii and instance count, and
+        # every gradient the backward returned (after an exchange: the arena's views, summed over the views)
+        names = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D") + (
+            ("dL_ddc",) if args.separate_sh else ()) + ("dL_dsh", "dL_dscales", "dL_drotations")
+        grads = dict(zip(names, last["grads"])) if last["grads"] is not None else dict(arena.views())
+        dumped = dump_outputs(args.dump_outputs, {
+            "color": last["color"], "invdepth": last["invdepth"], "radii": last["radii"],
+            "num_rendered": torch.tensor([int(last["num_rendered"])], dtype=torch.float64), **grads})
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     per_rank = [elapsed]
     if grouped:
@@ -561,9 +659,21 @@ def main():
         multi.update({"ranks_seen_by_backend": ranks_seen, "rank_devices": rank_devices,
                       "visible_devices_per_rank": ndev, "shared_gpu_rehearsal": rehearse})
 
+    head = headline(args, world, P, W, H, Kdeg, nr, elapsed, grouped, multi, ex, exchange) if rank == 0 else None
+    if dumped is not None:
+        head["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if not args.full:
+        if rank == 0:
+            head["host"] = host
+            if multi is not None:
+                head["multi_gpu"] = multi
+            print(json.dumps(head), flush=True)
+        if grouped:
+            dist.destroy_process_group()
+        return
+
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = world * P * args.steps / elapsed
+        ms_per_step = head["ms_per_step"]
         dom_ms = dom_total / dom_calls if dom_calls else 0.0  # HIP events on the launch stream, timed region
         # SURVEY.md 8d's algorithmic bytes of the kernel's own work (render_bwd: 44 I + 24 W H + 40 P); the
         # contract excludes zero-init memsets, so the fill that rides in the launch is reported beside it
@@ -610,35 +720,8 @@ def main():
             work[f"{stage}_pairs_per_s"] = pairs / (t_ms * 1e-3) if t_ms > 0 else None
         if census:
             work["pairs_per_instance"] = census["fwd_pairs_blended"] / nr if nr else None
-        # BASELINE.json's metric names the headline workload; another --config says its own
-        metric = ("Gaussian-splats/sec fwd+bwd @1080p, 1M Gaussians" if args.config == "1m_1080p_sh3" else
-                  f"Gaussian-splats/sec fwd+bwd @{W}x{H}, {P} Gaussians ({args.config}; not the headline metric)")
-        par = f"view-sharded x{world}"
-        if grouped:
-            # the backend that really ran (gloo in the one-GPU rehearsal, nccl = RCCL on ROCm)
-            be = "RCCL" if multi["backend"] == "nccl" else multi["backend"]
-            par += {"views": f" + {be} all-gather of " + ("sparse " if ex is not None and ex.sparse else "dense ")
-                    + "view blocks",
-                    "chunked": f" + {be} all-gathers of sparse view blocks in {args.exchange_chunks} Gaussian-range "
-                               "chunks, overlapped with the multi-view backward",
-                    "allreduce": f" + {be} all-reduce of the gradient arena"}[exchange]
         line = {
-            "metric": metric,
-            "value": value,
-            "unit": "Gaussian-splats/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "clock_ramp_s": args.ramp_seconds,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic (frustum-uniform Gaussians, SURVEY.md 8d; seed 0)",
-            "config": {"workload": args.config, "gaussians": P, "width": W, "height": H, "sh_degree": Kdeg,
-                       "num_rendered": nr, "views": "one per GPU, yaw 5 deg x rank", "parallelism": par,
-                       "sh_layout": "dc + rest (separate_sh)" if args.separate_sh else "one [P,M,3] tensor"},
+            **head,
             "roofline": {"kernel": dom, "bound": "hbm",
                          "achieved": own_traffic / (dom_ms * 1e-3) / 1e9 if counter_headline else achieved,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",

@@ -142,9 +142,12 @@ def preprocess(means3D, opacities, viewmatrix, projmatrix, campos, tanfovx, tanf
     conic = torch.stack([cyy * det_inv, -cxy * det_inv, cxx * det_inv], 1)
     opac = opacities[:, 0] * h_scale if antialiasing else opacities[:, 0]
     with torch.no_grad():
+        # the radius is an integer output: its square roots are taken in double and rounded to float, which is
+        # the correctly rounded float root the C oracle's sqrtf gives.  torch's float sqrt on the CPU is only
+        # accurate to an ulp and differs between CPU models, which moved one radius in a million on one host
         mid = 0.5 * (cxx + cyy)
-        root = torch.sqrt(torch.clamp_min(mid * mid - det, 0.1))
-        radius = torch.ceil(3.0 * torch.sqrt(torch.maximum(mid + root, mid - root)))
+        root = torch.sqrt(torch.clamp_min(mid * mid - det, 0.1).double()).to(F32)
+        radius = torch.ceil(3.0 * torch.sqrt(torch.maximum(mid + root, mid - root).double()).to(F32))
     # ndc2Pix (CR/auxiliary.h:43-46) evaluated in double, rounded to float
     x_pix = (((ndc[0].detach().double() + 1.0) * W - 1.0) * 0.5).to(F32)
     y_pix = (((ndc[1].detach().double() + 1.0) * H - 1.0) * 0.5).to(F32)

@@ -15,7 +15,7 @@ for cfg in $CONFIGS; do
       if [ "$lib" = base ]; then env_lib=""
       elif [ "${lib#env:}" != "$lib" ]; then env_lib=$(echo "${lib#env:}" | tr ',' ' '); name=$(echo "${lib#env:}" | sed 's#[^,]*/##g' | tr ',=' '-.')
       else env_lib="GSR_LIBRARY=$ROOT/$lib"; fi
-      env $env_lib timeout -k 10 300 python bench.py --config "$cfg" --no-cpu-baseline --no-census --steps 30 \
+      env $env_lib timeout -k 10 300 python bench.py --full --config "$cfg" --no-cpu-baseline --no-census --steps 30 \
         > "$OUT/${cfg}_${name}_$r.json" 2> "$OUT/${cfg}_${name}_$r.err"; rc=$?
       echo "$cfg $name round $r rc=$rc"; [ $rc -eq 0 ] || exit $rc
     done

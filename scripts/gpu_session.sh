@@ -23,35 +23,35 @@ for stage in "$@"; do
       timeout -k 10 1000 python -u -m pytest tests -m gpu -v -s --timeout 600 --timeout-method thread -k "fullsize" > "$OUT/pytest_full.log" 2>&1; rc=$?
       echo "full rc=$rc"; tail -5 "$OUT/pytest_full.log"; ok $rc || exit $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+      timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
       echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"; [ $rc -eq 0 ] || exit $rc ;;
     cpuonly)  # BASELINE configs[0]: the pure-PyTorch fallback forward on this host, no GPU touched
       timeout -k 10 600 python bench.py --cpu-only --config 10k_256_sh0 > "$OUT/cpu_only_10k_256_sh0.json" 2> "$OUT/cpu_only.err"; rc=$?
       echo "cpuonly rc=$rc"; cat "$OUT/cpu_only_10k_256_sh0.json"; [ $rc -eq 0 ] || exit $rc ;;
     benchquick)
-      timeout -k 10 600 python bench.py --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+      timeout -k 10 600 python bench.py --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
       echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"; [ $rc -eq 0 ] || exit $rc ;;
     variants)
       for lib in gaussian_splatting_amd/lib/libgsr_*.so; do
         v=$(basename $lib .so)
         GSR_LIBRARY=$ROOT/$lib timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -x > "$OUT/pytest_$v.log" 2>&1; rc=$?
         echo "variant $v tests rc=$rc: $(tail -1 $OUT/pytest_$v.log)"; ok $rc || exit $rc
-        GSR_LIBRARY=$ROOT/$lib timeout -k 10 300 python bench.py --no-cpu-baseline --steps 30 > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err"; rc=$?
+        GSR_LIBRARY=$ROOT/$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 30 > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err"; rc=$?
         echo "variant $v rc=$rc"; python -c "import json,sys; d=json.load(open('$OUT/bench_$v.json')); print(' ', d['ms_per_step'], d['stage_ms'])"; [ $rc -eq 0 ] || exit $rc
       done ;;
     cfg:*)  # bench + kernel stats of one config: cfg:<config>
       c=${stage#cfg:}
-      timeout -k 10 600 python bench.py --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"; rc=$?
+      timeout -k 10 600 python bench.py --full --config $c --no-cpu-baseline > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err"; rc=$?
       echo "bench $c rc=$rc"; cat "$OUT/bench_$c.json"; [ $rc -eq 0 ] || exit $rc
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$c" -o run -- \
-        python3 "$ROOT/bench.py" --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-census > "$OUT/prof_$c.log" 2>&1); rc=$?
+        python3 "$ROOT/bench.py" --full --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-census > "$OUT/prof_$c.log" 2>&1); rc=$?
       echo "prof $c rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     pmccfg:*)  # PMC passes of one config: pmccfg:<config>
       c=${stage#pmccfg:}
       bash scripts/pmc_session.sh "$TAG/pmc_$c" scripts/pmc_all.txt $c; rc=$?
       echo "pmc $c rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
-    launch2)  # bench.py --gpus 2 launching its own ranks (child torch.distributed.run), on one GPU with gloo
-      GSR_BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 2 \
+    launch2)  # bench.py --full --gpus 2 launching its own ranks (child torch.distributed.run), on one GPU with gloo
+      GSR_BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 5 --warmup 2 \
         > "$OUT/launch2.json" 2> "$OUT/launch2.err"; rc=$?
       echo "launch2 rc=$rc"; cat "$OUT/launch2.json"; tail -3 "$OUT/launch2.err"; [ $rc -eq 0 ] || exit $rc ;;
     stamps)  # per-workgroup timelines of the binning and render kernels (needs libgsr_stamps.so, built beforehand)
@@ -80,18 +80,18 @@ print('gsr_build_id', _lib.build_id(), 'tree', build.input_hash())"; } >> "$OUT/
     rehearse2)  # N=2 on one GPU (gloo collectives): the multi-rank bench path, both exchanges
       for ex in auto views dense allreduce; do
         GSR_BENCH_SHARE_GPU=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --exchange $ex \
+          --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 --exchange $ex \
           > "$OUT/rehearse2_$ex.json" 2> "$OUT/rehearse2_$ex.err"; rc=$?
         echo "rehearse2 $ex rc=$rc"; cat "$OUT/rehearse2_$ex.json"; [ $rc -eq 0 ] || exit $rc
       done ;;
     prof)
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-        python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-census > "$OUT/prof.log" 2>&1); rc=$?
+        python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-census > "$OUT/prof.log" 2>&1); rc=$?
       echo "prof rc=$rc"; tail -3 "$OUT/prof.log"; [ $rc -eq 0 ] || exit $rc ;;
     pmc)
       for ctr in "FETCH_SIZE" "WRITE_SIZE"; do
         (cd /tmp && timeout -k 10 600 rocprofv3 --pmc $ctr --output-format csv -d "$OUT/pmc_$ctr" -o run -- \
-          python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-census > "$OUT/pmc_$ctr.log" 2>&1); rc=$?
+          python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-census > "$OUT/pmc_$ctr.log" 2>&1); rc=$?
         echo "pmc $ctr rc=$rc"; tail -2 "$OUT/pmc_$ctr.log"; [ $rc -eq 0 ] || exit $rc
       done ;;
   esac

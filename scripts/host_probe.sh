@@ -7,7 +7,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/$1; R=${2:-8}; shift 2; mkdir -p "$OUT"
 for i in $(seq 1 $R); do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-census --steps 60 "$@" > "$OUT/b$i.json" 2> "$OUT/b$i.err" || exit $?
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-census --steps 60 "$@" > "$OUT/b$i.json" 2> "$OUT/b$i.err" || exit $?
   python - "$OUT/b$i.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); h = d["host"]

@@ -9,6 +9,6 @@ while read -r ctrs; do
   [ -z "$ctrs" ] && continue
   i=$((i+1))
   (cd /tmp && timeout -k 10 300 rocprofv3 --pmc $ctrs --output-format csv -d "$OUT/pmc$i" -o run -- \
-     python3 "$ROOT/bench.py" --config "$CFG" --steps 3 --warmup 1 --no-cpu-baseline --no-census > "$OUT/pmc$i.log" 2>&1); rc=$?
+     python3 "$ROOT/bench.py" --full --config "$CFG" --steps 3 --warmup 1 --no-cpu-baseline --no-census > "$OUT/pmc$i.log" 2>&1); rc=$?
   echo "pass $i ($ctrs) rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done < "$2"

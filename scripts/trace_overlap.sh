@@ -7,7 +7,7 @@ ROOT=$(pwd); TAG=$1; CFG=$2; shift 2
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/trace" -o run -- \
-   python3 "$ROOT/bench.py" --config "$CFG" --steps 5 --warmup 2 --no-cpu-baseline --no-census > "$OUT/trace.log" 2>&1) || exit 1
+   python3 "$ROOT/bench.py" --full --config "$CFG" --steps 5 --warmup 2 --no-cpu-baseline --no-census > "$OUT/trace.log" 2>&1) || exit 1
 python3 - "$OUT/trace/run_kernel_trace.csv" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -163,12 +163,20 @@ SMALL_CASES = [
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 RASTER_FIXTURES = sorted(f[len("raster_"):-len(".npz")] for f in os.listdir(GOLDEN)
-                         if f.startswith("raster_") and f.endswith(".npz"))
+                         if f.startswith("raster_") and f.endswith(".npz") and not f.endswith(".images.npz"))
+
+
+class _Merged(dict):
+    files = property(lambda self: list(self))
 
 
 def load_raster(name):
-    """A rasterizer golden vector (tests/golden/make_golden.py): (inp, expected, (grad_color, grad_invdepth))."""
-    z = np.load(os.path.join(GOLDEN, f"raster_{name}.npz"))
+    """A rasterizer golden vector (tests/golden/make_golden.py): (inp, expected, (grad_color, grad_invdepth)).
+    A vector too large for one file keeps its output images beside it in raster_<name>.images.npz."""
+    z = _Merged(np.load(os.path.join(GOLDEN, f"raster_{name}.npz")))
+    images = os.path.join(GOLDEN, f"raster_{name}.images.npz")
+    if os.path.exists(images):
+        z.update(np.load(images))
     inp = dict(bg=None, means3D=None, opacities=None, shs=None, sh_degree=0, scales=None, rotations=None,
                colors_precomp=None, cov3D_precomp=None)
     for k in z.files:

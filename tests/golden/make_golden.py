@@ -20,6 +20,11 @@ Two kinds of vectors, both small .npz files of inputs and expected outputs:
                   compute_cov3D_python (gaussian_renderer/__init__.py:86-87); compiled from the
                   reference's source with "cuda" read as "cpu".  Pins the oracle's computeCov3D
                   and the HIP cov3D_precomp path
+     densify_reference.npz   scene/gaussian_model.py densify_and_prune / add_densification_stats (compiled the
+                  same way) on the seeded inputs of tests/test_densify.py: pins oracle/densify.py
+     ply_reference_*.ply, ply_reference.npz   scene/dataset_readers.py storePly / fetchPly and
+                  GaussianModel.save_ply / construct_list_of_attributes, run through this repository's
+                  drop-in plyfile: the files they wrote and what they read back (tests/test_ply.py)
    These pin the camera conventions, the SH polynomial and the loss-gradient convention of the
    oracle and the HIP path.  The reference's rasterizer itself cannot run here (CUDA source,
    no nvcc, and BACKWARD::render is missing from the source; SURVEY.md section 8c).
@@ -186,6 +191,162 @@ def make_cov3d_vectors(reference):
     np.savez_compressed(os.path.join(HERE, "cov3d.npz"), **out)
 
 
+def _reference_gaussian_model(reference):
+    """GaussianModel (scene/gaussian_model.py) and build_rotation / strip_symmetric / ...
+    (utils/general_utils.py) compiled from the reference's source with the literal device "cuda" read as
+    "cpu" -- the only change -- so its densification runs on a CPU-only host."""
+    import ast
+
+    from torch import nn
+
+    from gaussian_splatting_amd.ply import BasicPointCloud
+
+    ns = {"torch": torch, "nn": nn, "np": np, "os": os, "BasicPointCloud": BasicPointCloud}
+    gu = ast.parse(open(os.path.join(reference, "utils/general_utils.py")).read())
+    funcs = [n for n in gu.body if isinstance(n, ast.FunctionDef)]
+    exec(compile(_CudaToCpu().visit(ast.Module(body=funcs, type_ignores=[])), "general_utils", "exec"), ns)
+    gm = ast.parse(open(os.path.join(reference, "scene/gaussian_model.py")).read())
+    cls = [n for n in gm.body if isinstance(n, ast.ClassDef) and n.name == "GaussianModel"]
+    exec(compile(_CudaToCpu().visit(ast.Module(body=cls, type_ignores=[])), "gaussian_model", "exec"), ns)
+    return ns["GaussianModel"]
+
+
+def _source_rows(out, src):
+    """For every row of ``out`` the index of the bitwise-equal row of ``src`` (-1 for an all-zero row that
+    is no row of ``src``); raises when a row is neither."""
+    key = {r.tobytes(): i for i, r in enumerate(src.reshape(len(src), -1))}
+    assert len(key) == len(src), "source rows are not unique"
+    idx = np.empty(len(out), np.int32)
+    for j, r in enumerate(out.reshape(len(out), -1)):
+        i = key.get(r.tobytes())
+        if i is None:
+            assert not r.any(), j
+            i = -1
+        idx[j] = i
+    return idx
+
+
+def make_densify_vectors(reference):
+    """densify_reference.npz: the reference's own add_densification_stats (with train.py:212-213) and
+    densify_and_prune (scene/gaussian_model.py) on the inputs of tests/test_densify.py
+    test_oracle_matches_reference_code, per case ``s<max_screen>_m<moments>``:
+      accum / denom / max_radii   the statistics after add_densification_stats
+      samples                     the normal samples densify_and_split draws (CPU generator, seed 123)
+      xyz / scaling               the two parameters densification computes, as the reference returns them
+      rows                        for every output Gaussian the input row its f_dc / f_rest / opacity / rotation
+                                  equal bit for bit (checked here for all four)
+      moment_rows                 the same for the optimizer's exp_avg / exp_avg_sq of all six groups
+                                  (-1: zeros, a new Gaussian), checked here for all twelve
+    so the test rebuilds the reference's full output from its own seeded inputs."""
+    from torch import nn
+
+    from oracle import densify as od
+    from tests import test_densify as td
+
+    GM = _reference_gaussian_model(reference)
+    out = {}
+    for max_screen, moments in td.REFERENCE_CASES:
+        tag = td.reference_tag(max_screen, moments)
+        P = td.REFERENCE_P
+        params, mom, accum, denom = td._case(P, 11, moments)
+        m = GM(3)
+        for k, a in td.ATTR.items():
+            setattr(m, a, nn.Parameter(torch.tensor(params[k]).requires_grad_(True)))
+        m.optimizer = torch.optim.Adam([{"params": [getattr(m, td.ATTR[k])], "lr": 1e-3, "name": k} for k in td.ATTR],
+                                       lr=0.0, eps=1e-15)
+        if mom is not None:
+            for k, a in td.ATTR.items():
+                m.optimizer.state[getattr(m, a)] = {"step": torch.tensor(3.0), "exp_avg": torch.tensor(mom[k][0]),
+                                                    "exp_avg_sq": torch.tensor(mom[k][1])}
+        m.percent_dense = 0.01
+        # the statistics through the reference's add_densification_stats and train.py:212-213
+        vg, radii = td.reference_stats_inputs(P)
+        m.xyz_gradient_accum = torch.tensor(accum).reshape(P, 1).clone()
+        m.denom = torch.tensor(denom).reshape(P, 1).clone()
+        m.max_radii2D = torch.zeros(P)
+        vpt = torch.zeros(P, 3, requires_grad=True)
+        vpt.grad = torch.tensor(vg)
+        vis = torch.tensor(radii) > 0
+        m.max_radii2D[vis] = torch.max(m.max_radii2D[vis], torch.tensor(radii)[vis])
+        m.add_densification_stats(vpt, vis)
+        out[tag + "_accum"] = m.xyz_gradient_accum.numpy().copy()
+        out[tag + "_denom"] = m.denom.numpy().copy()
+        out[tag + "_max_radii"] = m.max_radii2D.numpy().copy()
+        # the samples the reference will draw: same seed, same stds, same call
+        st = od.State(params, mom or {}, out[tag + "_accum"], out[tag + "_denom"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            grads = st.accum / st.denom
+        grads[np.isnan(grads)] = 0
+        od.densify_and_clone(st, grads, 2e-4, 2.0, 0.01)
+        sel = od.split_mask(st, grads, 2e-4, 2.0, 0.01)
+        stds = torch.exp(torch.tensor(st.params["scaling"][sel])).repeat(2, 1)
+        torch.manual_seed(123)
+        out[tag + "_samples"] = torch.normal(mean=torch.zeros((stds.size(0), 3)), std=stds).numpy()
+        torch.manual_seed(123)
+        m.densify_and_prune(2e-4, 0.005, 2.0, max_screen, torch.ones(P, dtype=torch.int32))
+        got = {k: getattr(m, a).detach().numpy() for k, a in td.ATTR.items()}
+        out[tag + "_xyz"], out[tag + "_scaling"] = got["xyz"], got["scaling"]
+        rows = _source_rows(got["f_rest"], params["f_rest"])
+        assert (rows >= 0).all()
+        for k in ("f_dc", "f_rest", "opacity", "rotation"):
+            np.testing.assert_array_equal(got[k], params[k][rows], err_msg=k)
+        out[tag + "_rows"] = rows
+        if mom is not None:
+            state = {k: m.optimizer.state[getattr(m, a)] for k, a in td.ATTR.items()}
+            mrows = _source_rows(state["f_rest"]["exp_avg"].numpy(), mom["f_rest"][0])
+            for k in td.ATTR:
+                for j, name in enumerate(("exp_avg", "exp_avg_sq")):
+                    np.testing.assert_array_equal(state[k][name].numpy(), td.moment_rows(mom[k][j], mrows),
+                                                  err_msg=f"{k} {name}")
+            out[tag + "_moment_rows"] = mrows
+        out[tag + "_tmp_radii_is_none"] = np.array(m.tmp_radii is None)
+    np.savez_compressed(os.path.join(HERE, "densify_reference.npz"), **out)
+
+
+def make_ply_vectors(reference):
+    """The reference's own PLY code, compiled from its source files with this repository's drop-in
+    ``plyfile`` in their globals (the ``scene`` package itself needs cv2): ``storePly`` / ``fetchPly``
+    (scene/dataset_readers.py:120-143) and ``GaussianModel.construct_list_of_attributes`` / ``save_ply``
+    (scene/gaussian_model.py:288-321), on the inputs of tests/test_ply.py.  Stored: the two files they
+    wrote (ply_reference_store.ply, ply_reference_save.ply) and, in ply_reference.npz, what fetchPly read
+    back and the attribute list."""
+    import ast
+    import shutil
+    import tempfile
+
+    import plyfile
+
+    from gaussian_splatting_amd import ply
+    from tests import test_ply as tp
+
+    assert os.path.dirname(os.path.dirname(os.path.abspath(plyfile.__file__))) == ROOT
+    ns = {"np": np, "os": os, "PlyData": plyfile.PlyData, "PlyElement": plyfile.PlyElement,
+          "BasicPointCloud": ply.BasicPointCloud, "mkdir_p": lambda d: os.makedirs(d, exist_ok=True)}
+    wanted = {"storePly", "fetchPly", "construct_list_of_attributes", "save_ply"}
+    for f in ("scene/dataset_readers.py", "scene/gaussian_model.py"):
+        tree = ast.parse(open(os.path.join(reference, f)).read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.FunctionDef) and node.name in wanted and node.name not in ns:
+                exec(compile(ast.Module(body=[node], type_ignores=[]), os.path.join(reference, f), "exec"), ns)
+    assert wanted <= set(ns), wanted - set(ns)
+    tmp = tempfile.mkdtemp()
+    try:
+        xyz, rgb = tp.reference_store_inputs()
+        a = os.path.join(tmp, "ref.ply")
+        ns["storePly"](a, xyz, rgb)
+        pc = ns["fetchPly"](a)
+        shutil.copyfile(a, os.path.join(HERE, "ply_reference_store.ply"))
+        src = tp.reference_save_model()
+        src.construct_list_of_attributes = lambda: ns["construct_list_of_attributes"](src)
+        b = os.path.join(tmp, "ref", "point_cloud.ply")
+        ns["save_ply"](src, b)
+        shutil.copyfile(b, os.path.join(HERE, "ply_reference_save.ply"))
+        np.savez_compressed(os.path.join(HERE, "ply_reference.npz"), fetch_points=pc.points, fetch_colors=pc.colors,
+                            fetch_normals=pc.normals, attributes=np.array(ns["construct_list_of_attributes"](src)))
+    finally:
+        shutil.rmtree(tmp)
+
+
 def make_raster_vectors():
     from tests import common as C
     from gaussian_splatting_amd import synthetic as syn
@@ -220,13 +381,31 @@ def save_raster(name, inp, C, with_backward):
         g = ref.handle.backward(gc.double().numpy(), gd.double().numpy(), nthreads=os.cpu_count())
         for k in C.GRAD_NAMES:
             out["out_" + k] = g[k].astype(np.float32)
-    np.savez_compressed(os.path.join(HERE, f"raster_{name}.npz"), **out)
+    write_raster(name, out)
+
+
+IMAGE_KEYS = ("out_color", "out_invdepth")
+MAX_FIXTURE_BYTES = 1 << 20
+
+
+def write_raster(name, out):
+    """raster_<name>.npz; when that would pass 1 MiB, the output images go to raster_<name>.images.npz
+    (tests/common.py load_raster reads both)."""
+    path = os.path.join(HERE, f"raster_{name}.npz")
+    np.savez_compressed(path, **out)
+    if os.path.getsize(path) > MAX_FIXTURE_BYTES:
+        np.savez_compressed(path, **{k: v for k, v in out.items() if k not in IMAGE_KEYS})
+        np.savez_compressed(os.path.join(HERE, f"raster_{name}.images.npz"), **{k: out[k] for k in IMAGE_KEYS})
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--only", choices=("densify", "ply"), help="write only these vectors, leave the others as they are")
     args = ap.parse_args()
+    if args.only:
+        {"densify": make_densify_vectors, "ply": make_ply_vectors}[args.only](args.reference)
+        return
     sys.path.insert(0, args.reference)
     from utils import graphics_utils as gu, loss_utils, sh_utils  # the reference's own Python
 
@@ -235,6 +414,8 @@ def main():
     make_ssim_vectors(loss_utils)
     sys.path.remove(args.reference)
     make_cov3d_vectors(args.reference)
+    make_densify_vectors(args.reference)
+    make_ply_vectors(args.reference)
     make_sh_vectors(sh_utils)
     make_raster_vectors()
     for f in sorted(os.listdir(HERE)):
