@@ -35,14 +35,101 @@ class Case:
     z_range: tuple = (2.0, 8.0)
     opacity_std: float = 1.5
     extra: dict = field(default_factory=dict)
+    # general camera pose (make_pose_camera); any of these makes the case a pose case, whose scene is generated
+    # in the camera's own frame and mapped to world space by the camera-to-world pose
+    pitch: float = 0.0
+    roll: float = 0.0
+    center: Optional[tuple] = None  # camera centre in world space (pose cases: default the origin)
+    focal_y: Optional[float] = None  # default: focal (square pixels)
+    principal: tuple = (0.0, 0.0)  # added to P[0,2], P[1,2] (NDC units)
+    xy_spread: float = 1.1  # the scene spans +-xy_spread * tanfov * z
+
+
+def is_pose_case(case: Case) -> bool:
+    return (case.pitch != 0.0 or case.roll != 0.0 or case.center is not None or case.focal_y is not None
+            or tuple(case.principal) != (0.0, 0.0))
+
+
+def pose_rotation(yaw: float, pitch: float, roll: float) -> np.ndarray:
+    """Camera-to-world rotation Ry(yaw) Rx(pitch) Rz(roll), degrees, float64; Ry is make_camera's."""
+    cy, sy = math.cos(math.radians(yaw)), math.sin(math.radians(yaw))
+    cx, sx = math.cos(math.radians(pitch)), math.sin(math.radians(pitch))
+    cz, sz = math.cos(math.radians(roll)), math.sin(math.radians(roll))
+    Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+    Rz = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+    return Ry @ Rx @ Rz
+
+
+def make_pose_camera(W, H, fx, fy, yaw, pitch, roll, center, principal=(0, 0)) -> syn.Camera:
+    """A pinhole camera at ``center`` (world space) with camera-to-world rotation Ry Rx Rz (degrees), focal lengths
+    fx != fy in pixels and a principal-point offset, by the conventions of synthetic.make_camera:
+    viewmatrix = getWorld2View2(R, T)^T, projmatrix = viewmatrix @ P^T, campos = inverse(viewmatrix)[3, :3]."""
+    fovx = 2 * math.atan(W / (2 * fx))  # focal2fov
+    fovy = 2 * math.atan(H / (2 * fy))
+    R_c2w = pose_rotation(yaw, pitch, roll)
+    T = -R_c2w.T @ np.asarray(center, np.float64)
+    wv = torch.tensor(syn.world2view(R_c2w, T)).transpose(0, 1).contiguous()
+    P = syn.projection(syn.ZNEAR, syn.ZFAR, fovx, fovy)
+    P[0, 2] += principal[0]
+    P[1, 2] += principal[1]
+    pm = torch.tensor(P).transpose(0, 1)
+    full = (wv.unsqueeze(0).bmm(pm.unsqueeze(0))).squeeze(0).contiguous()
+    campos = wv.inverse()[3, :3].contiguous()
+    return syn.Camera(W, H, math.tan(fovx * 0.5), math.tan(fovy * 0.5), wv, full, campos)
+
+
+def case_pose(case: Case):
+    """(camera-to-world rotation [3,3] float64, camera centre [3] float64) of a case's camera."""
+    if not is_pose_case(case):  # make_camera: yawed about +y around (0, 0, 7)
+        R = pose_rotation(case.yaw, 0.0, 0.0)
+        return R, np.array([0.0, 0.0, 7.0]) + R @ np.array([0.0, 0.0, -7.0])
+    return pose_rotation(case.yaw, case.pitch, case.roll), np.asarray(case.center or (0.0, 0.0, 0.0), np.float64)
+
+
+def case_camera(case: Case) -> syn.Camera:
+    if not is_pose_case(case):
+        return syn.make_camera(case.W, case.H, case.focal, case.yaw)
+    center = case_pose(case)[1]
+    return make_pose_camera(case.W, case.H, case.focal, case.focal_y if case.focal_y is not None else case.focal,
+                            case.yaw, case.pitch, case.roll, center, case.principal)
+
+
+def camera_frame_scene(case: Case, cam: syn.Camera) -> syn.Scene:
+    """synthetic.make_scene's recipe (same draws in the same order) with xy_spread in place of 1.1, in the frame of
+    ``cam`` (x, y within +-xy_spread * tanfov * z, z in z_range)."""
+    P = case.P
+    g = torch.Generator().manual_seed(case.seed)
+    z = torch.empty(P).uniform_(case.z_range[0], case.z_range[1], generator=g)
+    x = torch.empty(P).uniform_(-case.xy_spread, case.xy_spread, generator=g) * cam.tanfovx * z
+    y = torch.empty(P).uniform_(-case.xy_spread, case.xy_spread, generator=g) * cam.tanfovy * z
+    means = torch.stack([x, y, z], 1)
+    lo, hi = math.log(case.scale_range[0]), math.log(case.scale_range[1])
+    scales = torch.exp(torch.empty(P, 3).uniform_(lo, hi, generator=g))
+    rots = torch.nn.functional.normalize(torch.randn(P, 4, generator=g), dim=1)
+    opac = torch.sigmoid(torch.randn(P, 1, generator=g) * case.opacity_std)
+    shs = torch.randn(P, 16, 3, generator=g) * 0.05
+    shs[:, 0, :] = torch.randn(P, 3, generator=g) * 0.5
+    return syn.Scene(means.contiguous(), shs.contiguous(), opac.contiguous(), scales.contiguous(), rots.contiguous(), 3)
+
+
+def to_world(means_cam: torch.Tensor, R_c2w: np.ndarray, center: np.ndarray) -> torch.Tensor:
+    """Camera-frame points to world space (float64 arithmetic, stored float32)."""
+    return torch.from_numpy((means_cam.double().numpy() @ R_c2w.T + center).astype(np.float32)).contiguous()
 
 
 def build(case: Case):
     """Inputs as torch CPU float32 tensors (scene + camera + settings)."""
-    cam = syn.make_camera(case.W, case.H, case.focal, case.yaw)
-    base = syn.make_camera(case.W, case.H, case.focal, 0.0)
-    sc = syn.make_scene(case.P, base, sh_degree=3, seed=case.seed, scale_range=case.scale_range,
-                        opacity_std=case.opacity_std, z_range=case.z_range)
+    cam = case_camera(case)
+    if is_pose_case(case):
+        sc = camera_frame_scene(case, cam)
+        sc.means3D = to_world(sc.means3D, *case_pose(case))
+    elif case.xy_spread != 1.1:
+        sc = camera_frame_scene(case, syn.make_camera(case.W, case.H, case.focal, 0.0))
+    else:
+        base = syn.make_camera(case.W, case.H, case.focal, 0.0)
+        sc = syn.make_scene(case.P, base, sh_degree=3, seed=case.seed, scale_range=case.scale_range,
+                            opacity_std=case.opacity_std, z_range=case.z_range)
     M = case.M if case.M is not None else 16
     shs = sc.shs[:, :M, :].contiguous()
     inp = dict(
@@ -159,6 +246,56 @@ SMALL_CASES = [
     Case("lists_4k_8k", P=10000, W=32, H=32, scale_range=(0.1, 0.4)),
     Case("lists_over_8k", P=10000, W=16, H=16, scale_range=(0.1, 0.4)),
 ]
+
+# General camera poses (tests/golden/camera_pose.npz pins make_pose_camera against the reference's own Python).
+# A separate list: tests index SMALL_CASES by position.
+_GENERAL = dict(P=300, W=64, H=48, yaw=-18.0, pitch=12.0, roll=25.0, center=(0.3, -0.4, 0.2), focal=60.0, focal_y=75.0)
+POSE_CASES = [
+    Case("pose_general", **_GENERAL),
+    Case("pose_roll90", P=300, W=64, H=48, roll=90.0),  # the view rotation is a signed permutation
+    Case("pose_pitch", P=300, W=64, H=48, pitch=20.0, center=(0.0, 0.5, 0.0)),
+    Case("pose_aniso_focal", P=300, W=64, H=48, focal=50.0, focal_y=80.0),  # identity pose
+    Case("pose_back", P=300, W=64, H=48, yaw=160.0, pitch=-10.0),  # viewmatrix[10] < 0
+    Case("pose_principal", principal=(0.2, -0.1), **_GENERAL),
+    Case("pose_clamped", xy_spread=1.6, **_GENERAL),  # x/z, y/z beyond 1.3 tanfov (tests assert it)
+    Case("pose_general_aa", antialiasing=True, **_GENERAL),
+    Case("pose_general_cov3d", mode_cov="precomp", **_GENERAL),
+    Case("pose_general_precomp", mode_color="precomp", **_GENERAL),
+    Case("pose_general_sh1", sh_degree=1, **_GENERAL),  # M = 16, D < 3: the global-memory SH path
+]
+
+
+def pose_case(name: str) -> Case:
+    return next(c for c in POSE_CASES if c.name == name)
+
+
+def assert_clamp_preconditions(inp, ref):
+    """pose_clamped tests something only if visible Gaussians (radius > 0) lie beyond 1.3 tanfov in view-space
+    x/z alone, in y/z alone and in both, so that the limx and limy clamps of cov2D (CR/forward.cu:82-90) and the
+    x / y gradient masks of its backward each act alone and together.  View-space means are formed here from the
+    view matrix in float64 and checked against the oracle's depths."""
+    V = inp["viewmatrix"].double().numpy()
+    pv = np.concatenate([inp["means3D"].double().numpy(), np.ones((inp["means3D"].shape[0], 1))], 1) @ V[:, :3]
+    vis = ref.radii > 0
+    np.testing.assert_allclose(pv[vis, 2], ref.handle.geom()["depths"][vis], rtol=1e-5)
+    cx = np.abs(pv[:, 0] / pv[:, 2]) > 1.3 * inp["tanfovx"]
+    cy = np.abs(pv[:, 1] / pv[:, 2]) > 1.3 * inp["tanfovy"]
+    counts = int((vis & cx & ~cy).sum()), int((vis & cy & ~cx).sum()), int((vis & cx & cy).sum())
+    assert min(counts) >= 1, counts
+    return counts
+
+
+def rounding_flip_caps(inp, ref32, nthreads=1):
+    """Caps for the forward threshold-flip rule (tests/test_gpu_parity.py): how many pixels may lie over 1e-5,
+    and how many may end their walk at another contributor, before "every such pixel is explained" stops being
+    believable.  Derived from the references alone: the same two counts for the f32 oracle against the f64
+    oracle on these inputs -- the flips that rounding alone produces -- times 4, plus 4 pixels, as slack for a
+    different but legitimate rounding order.  Returns (cap_over, cap_n_contrib, (oracle_over, oracle_n_contrib))."""
+    ref64 = run_oracle(inp, precision="f64", nthreads=nthreads)
+    d = np.maximum(np.abs(ref32.color - ref64.color).max(0), np.abs(ref32.invdepth - ref64.invdepth)[0])
+    over = int((d > 1e-5).sum())
+    nc = int((ref32.handle.image()["n_contrib"] != ref64.handle.image()["n_contrib"]).sum())
+    return 4 * over + 4, 4 * nc + 4, (over, nc)
 
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

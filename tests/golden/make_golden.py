@@ -8,6 +8,8 @@ Two kinds of vectors, both small .npz files of inputs and expected outputs:
    (they run on CPU; SURVEY.md section 8c lists them):
      camera.npz   utils/graphics_utils.py:38-71 getWorld2View2 / getProjectionMatrix composed as
                   scene/cameras.py:86-89 (world_view_transform, full_proj_transform, camera_center)
+     camera_pose.npz  the same two functions, raw outputs, for the general poses of tests/common.py
+                  POSE_CASES (rotation Ry Rx Rz, centre off the origin, fx != fy): pins make_pose_camera
      sh_eval.npz  utils/sh_utils.py:57-112 eval_sh, composed as gaussian_renderer/__init__.py:86-96
                   (convert_SHs_python: colours = clamp_min(eval_sh(...) + 0.5, 0))
      l1_grad.npz  utils/loss_utils.py:16-19 l1_loss, its autograd gradient (the upstream-gradient
@@ -56,7 +58,8 @@ sys.path.insert(0, ROOT)
 CAMERAS = [(64, 48, 60.0, 0.0), (37, 23, 30.0, 15.0), (1920, 1080, 1600.0, 5.0), (256, 256, 213.0, -35.0)]
 
 RASTER_CASES = ["sh3_scalerot", "ragged_37x23", "sh1_of_16", "colors_precomp", "cov3d_precomp", "antialiasing",
-                "background", "scale_modifier", "yawed_view"]
+                "background", "scale_modifier", "yawed_view", "pose_general"]
+RASTER_POSE_CASES = ["pose_general"]  # those of tests/common.py POSE_CASES: --only raster_pose writes just these
 
 
 def camera_pose(yaw_deg: float, pivot_z: float = 7.0):
@@ -82,6 +85,49 @@ def make_camera_vectors(gu):
         out[f"cam{i}_projmatrix"] = full.numpy()
         out[f"cam{i}_campos"] = campos.numpy()
     np.savez_compressed(os.path.join(HERE, "camera.npz"), **out)
+
+
+# the distinct cameras of tests/common.py POSE_CASES (the other cases reuse pose_general's)
+POSE_CAMERAS = ["pose_general", "pose_roll90", "pose_pitch", "pose_aniso_focal", "pose_back", "pose_principal"]
+
+
+def make_camera_pose_vectors(reference):
+    """camera_pose.npz: per pose camera (one row each, "names") the inputs (W, H, fx, fy, yaw, pitch, roll,
+    centre, principal, fovx, fovy, R, T) and the reference's raw getWorld2View2(R, T) and
+    getProjectionMatrix(0.01, 100, fovx, fovy).  The reference's projection has no principal point; the test adds
+    the case's offset to P[0,2], P[1,2]."""
+    from tests import common as C
+
+    sys.path.insert(0, reference)
+    try:
+        from utils import graphics_utils as gu
+    finally:
+        sys.path.remove(reference)
+    rows = {k: [] for k in ("inputs", "R", "T", "world2view", "projection")}
+    for name in POSE_CAMERAS:
+        c = C.pose_case(name)
+        fy = c.focal_y if c.focal_y is not None else c.focal
+        R, center = C.case_pose(c)
+        T = -R.T @ center
+        fovx, fovy = gu.focal2fov(c.focal, c.W), gu.focal2fov(fy, c.H)
+        rows["inputs"].append(np.array([c.W, c.H, c.focal, fy, c.yaw, c.pitch, c.roll, *center, *c.principal,
+                                        fovx, fovy], np.float64))
+        rows["R"].append(R)
+        rows["T"].append(T)
+        rows["world2view"].append(gu.getWorld2View2(R, T))
+        rows["projection"].append(gu.getProjectionMatrix(znear=0.01, zfar=100.0, fovX=fovx, fovY=fovy).numpy())
+    out = {k: np.stack(v) for k, v in rows.items()}
+    out["names"] = np.array(POSE_CAMERAS)
+    np.savez_compressed(os.path.join(HERE, "camera_pose.npz"), **out)
+
+
+def make_raster_pose_vectors(reference=None):
+    """raster_pose_general.npz alone (the other raster vectors stay as they are)."""
+    from tests import common as C
+
+    for name in RASTER_POSE_CASES:
+        assert name in RASTER_CASES
+        save_raster(name, C.build(C.pose_case(name)), C, with_backward=True)
 
 
 def make_sh_vectors(sh_utils):
@@ -351,7 +397,7 @@ def make_raster_vectors():
     from tests import common as C
     from gaussian_splatting_amd import synthetic as syn
 
-    cases = {c.name: c for c in C.SMALL_CASES}
+    cases = {c.name: c for c in C.SMALL_CASES + C.POSE_CASES}
     for name in RASTER_CASES:
         inp = C.build(cases[name])
         save_raster(name, inp, C, with_backward=True)
@@ -401,10 +447,12 @@ def write_raster(name, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
-    ap.add_argument("--only", choices=("densify", "ply"), help="write only these vectors, leave the others as they are")
+    ap.add_argument("--only", choices=("densify", "ply", "camera_pose", "raster_pose"),
+                    help="write only these vectors, leave the others as they are")
     args = ap.parse_args()
     if args.only:
-        {"densify": make_densify_vectors, "ply": make_ply_vectors}[args.only](args.reference)
+        {"densify": make_densify_vectors, "ply": make_ply_vectors, "camera_pose": make_camera_pose_vectors,
+         "raster_pose": make_raster_pose_vectors}[args.only](args.reference)
         return
     sys.path.insert(0, args.reference)
     from utils import graphics_utils as gu, loss_utils, sh_utils  # the reference's own Python
@@ -417,6 +465,7 @@ def main():
     make_densify_vectors(args.reference)
     make_ply_vectors(args.reference)
     make_sh_vectors(sh_utils)
+    make_camera_pose_vectors(args.reference)
     make_raster_vectors()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):

@@ -68,6 +68,49 @@ def test_camera_matrices_match_reference():
     assert i >= 3
 
 
+def test_pose_camera_matches_reference():
+    """tests/common.py make_pose_camera (rotation Ry Rx Rz, centre off the origin, fx != fy, principal point)
+    against the reference's own getWorld2View2 / getProjectionMatrix on the same R, T, fovs
+    (tests/golden/camera_pose.npz), composed as scene/cameras.py:86-89.  The reference's projection has no
+    principal point: the case's offset is added to P[0,2], P[1,2] before the composition."""
+    z = _npz("camera_pose.npz")
+    names = [str(n) for n in z["names"]]
+    # every distinct camera of POSE_CASES is in the fixture: the other cases reuse pose_general's
+    reuse = [c for c in C.POSE_CASES if c.name not in names]
+    assert len(names) + len(reuse) == len(C.POSE_CASES) and len(names) >= 6
+    general = C.case_camera(C.pose_case("pose_general"))
+    for c in reuse:
+        cam = C.case_camera(c)
+        assert torch.equal(cam.viewmatrix, general.viewmatrix) and torch.equal(cam.projmatrix, general.projmatrix)
+        assert (cam.tanfovx, cam.tanfovy) == (general.tanfovx, general.tanfovy)
+    for i, name in enumerate(names):
+        W, H, fx, fy, yaw, pitch, roll, cx, cy, cz, px, py, fovx, fovy = z["inputs"][i]
+        case = C.pose_case(name)  # the fixture was made for this case's camera
+        assert (case.W, case.H, case.focal, case.yaw, case.pitch, case.roll) == (W, H, fx, yaw, pitch, roll)
+        assert tuple(case.principal) == (px, py) and (case.focal_y or case.focal) == fy
+        np.testing.assert_allclose(C.pose_rotation(yaw, pitch, roll), z["R"][i], rtol=0, atol=1e-15)
+        wv = torch.tensor(z["world2view"][i]).transpose(0, 1)
+        P = torch.tensor(z["projection"][i]).clone()
+        P[0, 2] += px
+        P[1, 2] += py
+        full = wv.unsqueeze(0).bmm(P.transpose(0, 1).unsqueeze(0)).squeeze(0)
+        campos = wv.inverse()[3, :3]
+        for cam in (C.make_pose_camera(int(W), int(H), fx, fy, yaw, pitch, roll, (cx, cy, cz), (px, py)),
+                    C.case_camera(case)):
+            np.testing.assert_allclose(cam.viewmatrix.numpy(), wv.numpy(), rtol=0, atol=2e-6)
+            np.testing.assert_allclose(cam.projmatrix.numpy(), full.numpy(), rtol=0, atol=2e-6)
+            np.testing.assert_allclose(cam.campos.numpy(), campos.numpy(), rtol=0, atol=2e-6)
+            np.testing.assert_allclose(cam.campos.numpy(), [cx, cy, cz], rtol=0, atol=2e-6)
+            assert abs(cam.tanfovx - np.tan(fovx / 2)) < 1e-12 and abs(cam.tanfovy - np.tan(fovy / 2)) < 1e-12
+        # what the yaw cameras never had: a y row, fx != fy
+        V = wv.numpy().reshape(-1)
+        if name == "pose_general":
+            assert all(abs(V[k]) > 0.04 for k in (1, 4, 6, 9)) and abs(V[5] - 1) > 0.05
+            assert all(abs(full.numpy().reshape(-1)[k]) > 0.05 for k in (1, 4, 7, 9))
+        if name == "pose_back":
+            assert V[10] < 0
+
+
 def _sh_inputs(z, deg, precomp):
     W, H, tx, ty = z["camera"]
     inp = dict(bg=torch.zeros(3), means3D=torch.from_numpy(z["means3D"]), opacities=torch.from_numpy(z["opacities"]),

@@ -49,7 +49,8 @@ VARIANTS = {
     "bwd_atomic=1,touched_run=4": dict(bwd_atomic=1, touched_run=4),
     "bwd_atomic=1,touched_run=32": dict(bwd_atomic=1, touched_run=32),
 }
-CASES = ["sh3_scalerot", "antialiasing", "dense_opaque", "lists_1k_2k", "lists_4k_8k", "lists_over_8k"]
+CASES = ["sh3_scalerot", "antialiasing", "dense_opaque", "lists_1k_2k", "lists_4k_8k", "lists_over_8k",
+         "pose_general"]  # (a general camera pose: every alternative path sees a y row, fx != fy)
 
 
 def _np(t):
@@ -80,7 +81,7 @@ def test_option_path_matches_oracle(variant, case_name, hint):
     from gaussian_splatting_amd import _C as CM
     from gaussian_splatting_amd import _lib
 
-    case = next(c for c in C.SMALL_CASES if c.name == case_name)
+    case = next(c for c in C.SMALL_CASES + C.POSE_CASES if c.name == case_name)
     inp = C.build(case)
     ref = C.run_oracle(inp)
     grads = (C.unit_grads(case.H, case.W), C.l1_grads(case.H, case.W))

@@ -24,10 +24,12 @@ def _to_np(t):
     return t.detach().float().cpu().numpy()
 
 
-@pytest.mark.parametrize("case", C.SMALL_CASES, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", C.SMALL_CASES + C.POSE_CASES, ids=lambda c: c.name)
 def test_forward_matches_oracle(case):
     inp = C.build(case)
     ref = C.run_oracle(inp)
+    if case.name == "pose_clamped":
+        C.assert_clamp_preconditions(inp, ref)
     nr, color, radii, geom, binning, img, invd = C.run_gpu_forward(inp)
     torch.cuda.synchronize()
     assert nr == ref.num_rendered
@@ -44,10 +46,12 @@ def test_forward_matches_oracle(case):
     np.testing.assert_allclose(_to_np(invd), ref.invdepth, atol=ATOL_FWD, rtol=0)
 
 
-@pytest.mark.parametrize("case", C.SMALL_CASES, ids=lambda c: c.name)
+@pytest.mark.parametrize("case", C.SMALL_CASES + C.POSE_CASES, ids=lambda c: c.name)
 def test_backward_matches_oracle(case):
     inp = C.build(case)
     ref = C.run_oracle(inp)
+    if case.name == "pose_clamped":
+        C.assert_clamp_preconditions(inp, ref)
     fwd = C.run_gpu_forward(inp)
     for grads, mode in ((C.unit_grads(case.H, case.W), "unit"), (C.l1_grads(case.H, case.W), "l1")):
         gc, gd = grads
@@ -173,12 +177,39 @@ def test_mark_visible():
     np.testing.assert_array_equal(vis.cpu().numpy(), exp)
 
 
+def test_mark_visible_general_pose():
+    """mark_visible under pose_general's camera (view-space z takes all three world coordinates), with a scene
+    that straddles the view z = 0.2 threshold: both outcomes occur, and some Gaussians lie close to it."""
+    import dataclasses
+
+    from gaussian_splatting_amd import _C
+    from oracle import oracle
+
+    inp = C.build(dataclasses.replace(C.pose_case("pose_general"), name="mv_pose", P=500, z_range=(-3.0, 6.0)))
+    V = inp["viewmatrix"].double().numpy()
+    z = inp["means3D"].double().numpy() @ V[:3, 2] + V[3, 2]
+    assert (z > 0.2).sum() > 100 and (z <= 0.2).sum() > 100 and (np.abs(z - 0.2) < 0.05).sum() >= 3
+    vis = _C.mark_visible(inp["means3D"].cuda(), inp["viewmatrix"].cuda(), inp["projmatrix"].cuda())
+    exp = oracle.mark_visible(inp["means3D"], inp["viewmatrix"])
+    np.testing.assert_array_equal(exp.astype(bool), z > 0.2)  # (no mean within float32 rounding of the threshold)
+    np.testing.assert_array_equal(vis.cpu().numpy(), exp)
+
+
 @pytest.mark.record_path
 def test_autograd_module_matches_direct_calls():
     """GaussianRasterizer through autograd == _C forward/backward, incl. means2D gradient."""
+    _autograd_module_vs_direct_calls(C.SMALL_CASES[0])
+
+
+@pytest.mark.record_path
+def test_autograd_module_matches_direct_calls_general_pose():
+    """The same under a general camera pose (the settings' matrices, campos and tanfovx != tanfovy * W / H)."""
+    _autograd_module_vs_direct_calls(C.pose_case("pose_general"))
+
+
+def _autograd_module_vs_direct_calls(case):
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 
-    case = C.SMALL_CASES[0]
     inp = C.build(case)
     dev = "cuda"
     settings = GaussianRasterizationSettings(
@@ -293,6 +324,14 @@ def test_matches_golden_fixture(name):
     nc_diff = st["n_contrib"].numpy() != ref32.handle.image()["n_contrib"].astype(np.int64)
     unexplained = (d > ATOL_FWD) & ~(near | nc_diff)
     assert not unexplained.any(), (name, int(unexplained.sum()), float(d[unexplained].max()))
+    # ... and the explained set is bounded: 4x the f32 oracle's own counts against the f64 oracle + 4 pixels
+    # (C.rounding_flip_caps).  Measured oracle counts (pixels over 1e-5, pixels with another n_contrib):
+    # 10k_256_sh0 (1, 0): caps 8 and 4; every other fixture (0, 0): caps 4 and 4
+    cap_over, cap_nc, oracle_counts = C.rounding_flip_caps(inp, ref32, nthreads=4)
+    print(f"[{name}] over 1e-5: {int((d > ATOL_FWD).sum())} (cap {cap_over}), n_contrib differs: "
+          f"{int(nc_diff.sum())} (cap {cap_nc}); f32 oracle vs f64 oracle {oracle_counts}")
+    assert int((d > ATOL_FWD).sum()) <= cap_over, (name, int((d > ATOL_FWD).sum()), cap_over)
+    assert int(nc_diff.sum()) <= cap_nc, (name, int(nc_diff.sum()), cap_nc)
     print(f"[{name}] pixels over 1e-5: {int((d > ATOL_FWD).sum())}, all explained; max|diff| elsewhere "
           f"{float(d[~(near | nc_diff)].max()) if (~(near | nc_diff)).any() else 0.0:.2e}")
     if grads is None:
@@ -447,6 +486,16 @@ def test_large_image(P, W, H):
     nc_diff = st["n_contrib"].numpy() != ref.handle.image()["n_contrib"].astype(np.int64)
     unexplained = (d > ATOL_FWD) & ~(near | nc_diff)
     assert not unexplained.any(), (int(unexplained.sum()), float(d[unexplained].max()))
+    # ... and the explained set is bounded: 4x the f32 oracle's own counts against the f64 oracle + 4 pixels
+    # (C.rounding_flip_caps).  Measured oracle counts (pixels over 1e-5, pixels with another n_contrib) -> caps:
+    #   2304x2048_sparse (55, 7) -> 224, 32      2304x2048_dense (206 or 207 by host, 16) -> 828 or 832, 68
+    #   5120x2048_global_cursors (1660, 32) -> 6644, 132
+    #   8400x64_wide (34, 7) -> 140, 32          64x8400_tall (26, 9) -> 108, 40
+    cap_over, cap_nc, oracle_counts = C.rounding_flip_caps(inp, ref, nthreads=8)
+    print(f"[large_image P={P} {W}x{H}] over 1e-5: {int((d > ATOL_FWD).sum())} (cap {cap_over}), n_contrib differs: "
+          f"{int(nc_diff.sum())} (cap {cap_nc}); f32 oracle vs f64 oracle {oracle_counts}")
+    assert int((d > ATOL_FWD).sum()) <= cap_over, (int((d > ATOL_FWD).sum()), cap_over)
+    assert int(nc_diff.sum()) <= cap_nc, (int(nc_diff.sum()), cap_nc)
     gc, gd = C.l1_grads(case.H, case.W)
     out = C.run_gpu_backward(inp, fwd, gc, gd)
     r = ref.handle.backward(gc, gd, nthreads=8)

@@ -24,7 +24,7 @@ CASES = [c for c in C.SMALL_CASES if c.name != "dense_opaque"] + [
     C.Case("dense_small", P=600, W=32, H=32, opacity_std=3.0, scale_range=(0.05, 0.3)),
     C.Case("clamped_fov", P=150, W=40, H=40, yaw=35.0),
     C.Case("near_plane", P=150, W=48, H=48, z_range=(0.1, 3.0)),
-]
+] + C.POSE_CASES  # general camera poses: a y row in the view rotation, fx != fy, a principal point
 
 
 def _run(case):
@@ -58,6 +58,16 @@ def test_backward_matches_autograd(case):
         return
     for k in CONIC:
         assert C.rel_err(og[k], tg[k]) <= 1e-5, (k, C.rel_err(og[k], tg[k]))
+
+
+def test_pose_clamped_has_clamped_gaussians():
+    """pose_clamped's own preconditions: visible Gaussians beyond 1.3 tanfov in view-space x alone, in y alone
+    and in both (seed 0: 10, 11 and 2), so the limx / limy clamps and their gradient masks are compared above."""
+    inp = C.build(C.pose_case("pose_clamped"))
+    for prec in ("f32", "f64"):
+        assert C.assert_clamp_preconditions(inp, C.run_oracle(inp, precision=prec)) == (10, 11, 2)
+    # the clamp bounds differ in x and y (fx != fy), and the other pose cases have no clamped Gaussian to hide behind
+    assert abs(inp["tanfovx"] / inp["tanfovy"] - 64 / 48) > 0.1
 
 
 def test_conic_epsilon_is_the_only_difference():

@@ -31,7 +31,10 @@ def _perturbed(inp, key, i, j, delta):
 @pytest.mark.parametrize("case", [C.Case("fd_sh3", P=60, W=40, H=32, sh_degree=3),
                                   C.Case("fd_yaw_bg", P=60, W=40, H=32, yaw=20.0, bg=(0.3, 0.6, 0.1)),
                                   C.Case("fd_precomp", P=60, W=40, H=32, mode_color="precomp",
-                                         mode_cov="precomp")], ids=lambda c: c.name)
+                                         mode_cov="precomp"),
+                                  # a general pose: rotation Ry Rx Rz, centre off the origin, fx != fy
+                                  C.Case("fd_pose_general", P=60, W=40, H=32, yaw=-18.0, pitch=12.0, roll=25.0,
+                                         center=(0.3, -0.4, 0.2), focal=60.0, focal_y=75.0)], ids=lambda c: c.name)
 def test_backward_matches_finite_differences(case):
     inp = C.build(case)
     inp = {k: (v.double() if torch.is_tensor(v) else v) for k, v in inp.items()}

@@ -22,6 +22,9 @@ CASES = [
     C.Case("sep_sh2_M9", P=250, W=48, H=40, sh_degree=2, M=9),  # generic path, rest of 8
     C.Case("sep_sh0_M1", P=250, W=48, H=40, sh_degree=0, M=1),  # dc only, empty rest
     C.Case("sep_antialiasing", P=300, W=64, H=48, antialiasing=True),
+    # general camera poses through the dc + rest LDS path
+    C.pose_case("pose_general"),
+    C.pose_case("pose_general_aa"),
 ]
 
 

@@ -49,7 +49,8 @@ def test_config1_forward_10k_256_sh0():
     _check_forward(res, C.run_oracle(inp, nthreads=4))
 
 
-@pytest.mark.parametrize("case", [c for c in C.SMALL_CASES if c.P <= 2000], ids=lambda c: c.name)
+@pytest.mark.parametrize("case", [c for c in C.SMALL_CASES if c.P <= 2000] + [C.pose_case("pose_general")],
+                         ids=lambda c: c.name)
 def test_forward_backward_matches_oracle(case):
     inp = C.build(case)
     gc, gd = C.unit_grads(case.H, case.W)

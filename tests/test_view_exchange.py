@@ -11,6 +11,7 @@ GPU the views are rendered one after another, so this checks the arithmetic the 
 * a view block's dL/dmeans2D equals the backward's;
 * the CPU gloo test checks the in-place all-gather layout of the exchange buffer.
 """
+import dataclasses
 import os
 import socket
 
@@ -92,11 +93,15 @@ def _views_backward(t, blocks, split, dev, flags=None, live=None, out=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("split", [False, True])
 @pytest.mark.parametrize("case_kw", [dict(P=300, W=64, H=48), dict(P=250, W=48, H=40, sh_degree=1),
-                                     dict(P=300, W=64, H=48, antialiasing=True)])
+                                     dict(P=300, W=64, H=48, antialiasing=True),
+                                     # tests/common.py pose_general: a general camera pose, fx != fy
+                                     dict(P=300, W=64, H=48, yaw=-18.0, pitch=12.0, roll=25.0,
+                                          center=(0.3, -0.4, 0.2), focal=60.0, focal_y=75.0)])
 @pytest.mark.record_path
 def test_one_view_equals_single_view(case_kw, split):
     dev = torch.device("cuda", 0)
-    inp, case = _view_inputs(case_kw, 0.0, dev)
+    case_kw = dict(case_kw)
+    inp, case = _view_inputs(case_kw, case_kw.pop("yaw", 0.0), dev)
     single, block, t = _single_and_block(inp, case, dev, split)
     got = _views_backward(t, block.view(1, -1), split, dev)
     torch.cuda.synchronize()
@@ -125,6 +130,56 @@ def test_views_sum_equals_sum_of_single_views(split):
         ref = sums[k]
         err = (got[k] - ref).abs().max().item()
         scale = ref.abs().max().item()
+        assert err <= 2e-6 * max(scale, 1e-3) + 1e-9, (k, err, scale)
+
+
+def _expected_header(inp):
+    """The 41 header floats of a view block (csrc/gsr_common.h kViewCam*), built on the host from the view's
+    inputs: viewmatrix (16), projmatrix (16), campos (3), tan fov x / y, focal x / y (W / (2 tanfovx),
+    H / (2 tanfovy) in float32, CR/rasterizer_impl.cu:253-254), and the antialiasing and inverse-depth-gradient
+    flags as integer bits."""
+    f = np.float32
+    tx, ty = f(inp["tanfovx"]), f(inp["tanfovy"])
+    head = np.concatenate([inp["viewmatrix"].numpy().reshape(-1), inp["projmatrix"].numpy().reshape(-1),
+                           inp["campos"].numpy().reshape(-1),
+                           np.array([tx, ty, f(inp["W"]) / (f(2.0) * tx), f(inp["H"]) / (f(2.0) * ty)], f)]).astype(f)
+    return np.concatenate([head.view(np.uint32), np.array([int(inp["antialiasing"]), 1], np.uint32)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.record_path
+def test_views_general_poses(split):
+    """Four views of one scene under four different general poses and four different focal_y (pose_general,
+    pose_roll90, pose_pitch, pose_back of tests/common.py): the scene is the union of four parts, each generated
+    in one camera's frame, so every view sees a part of it and culls another.  gauss_backward_views over the four
+    blocks equals the sum of the four single-view backwards, and each block's camera header is the one built on
+    the host from that view's own matrices."""
+    dev = torch.device("cuda", 0)
+    cases = [dataclasses.replace(C.pose_case(n), P=300, seed=v, **kw) for v, (n, kw) in enumerate(
+        (("pose_general", {}), ("pose_roll90", dict(focal_y=66.0)), ("pose_pitch", dict(focal_y=54.0)),
+         ("pose_back", dict(focal_y=80.0))))]
+    assert len({(c.focal_y, c.yaw, c.pitch, c.roll) for c in cases}) == 4
+    parts = [C.build(c) for c in cases]
+    scene = {k: torch.cat([p[k] for p in parts]) for k in ("means3D", "opacities", "shs", "scales", "rotations")}
+    P = scene["means3D"].shape[0]
+    blocks, sums = [], None
+    for case, part in zip(cases, parts):
+        inp = dict(part, **scene)
+        single, block, t = _single_and_block(inp, case, dev, split)
+        seen = int(_live(block, P).sum())
+        assert case.P // 3 <= seen < P - case.P // 3, (case.name, seen)  # sees a part, culls a part
+        got = block[:41].cpu().numpy().view(np.uint32)
+        np.testing.assert_array_equal(got, _expected_header(inp), err_msg=case.name)
+        blocks.append(block)
+        sums = {k: single[k].clone() for k in single} if sums is None else {k: sums[k] + single[k] for k in sums}
+    got = _views_backward(t, torch.stack(blocks), split, dev)
+    torch.cuda.synchronize()
+    for k in got:
+        ref = sums[k]
+        err = (got[k] - ref).abs().max().item()
+        scale = ref.abs().max().item()
+        assert scale > 0, k
         assert err <= 2e-6 * max(scale, 1e-3) + 1e-9, (k, err, scale)
 
 
