@@ -1,4 +1,7 @@
-// api.hip -- host orchestration and the extern "C" boundary (include/gsr.h).
+// api.hip -- the rasterizer's host orchestration and its part of the extern "C" boundary (include/gsr.h):
+// the forward and backward, the runtime options, the profile, census and debug entry points, and the one
+// definition of the error message and the stage profiler that host.h declares.  The other components' entry
+// points are beside their kernels (ssim.hip, knn.hip, adam.hip, densify.hip, views.hip; ply.cpp).
 //
 // Forward stage order mirrors CudaRasterizer::Rasterizer::forward
 // (CR/rasterizer_impl.cu:227-370); the stages themselves are this project's
@@ -18,18 +21,15 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/gsr.h"
-#include "../../include/gsr_knn.h"
-#include "../../include/gsr_ssim.h"
-#include "../../include/gsr_adam.h"
-#include "../../include/gsr_densify.h"
+#include "host.h"
 #include "kernels.h"
 
 namespace {
-
 thread_local char g_err[1024] = "";
+}  // namespace
 
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+namespace gsr {
+
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -38,87 +38,20 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-}  // namespace
+void clear_error() { (void)fail(GSR_OK, "%s", ""); }  // (fail is the buffer's only writer)
 
-namespace gsr {
-// for host-only translation units (ply.cpp): set gsr_last_error()'s message, return `code`
-int set_error(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+Profiler g_prof;
+
 }  // namespace gsr
+
+using namespace gsr;
 
 namespace {
 
-#define HIP_TRY(expr, stage)                                                                                    \
-    do {                                                                                                        \
-        hipError_t _e = (expr);                                                                                 \
-        if (_e != hipSuccess) return fail(GSR_ERR_HIP, "%s: %s", stage, hipGetErrorString(_e));                 \
-    } while (0)
-
-// ---- stage profiler -----------------------------------------------------------
-enum Stage {
-    ST_PREPROCESS = 0,
-    ST_BIN_COUNT,    // K1 + K2 of binning.hip
-    ST_BIN_SCATTER,  // K3
-    ST_TILE_SORT,    // K4
-    ST_RENDER_FWD,
-    ST_RENDER_BWD,
-    ST_GAUSS_REDUCE,
-    ST_GAUSS_BWD,
-    ST_COUNT
-};
 const char* kStageNames[ST_COUNT] = {"preprocess", "bin_count",  "bin_scatter",  "tile_sort",
                                      "render_fwd", "render_bwd", "gauss_reduce", "gauss_bwd"};
 
-struct Profiler {
-    unsigned mask = 0;  // bit s: record stage s
-    std::mutex mu;
-    struct Pending {
-        int stage;
-        hipEvent_t a, b;
-    };
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> pool;
-    double total_ms[ST_COUNT] = {};
-    long long calls[ST_COUNT] = {};
-    hipEvent_t get() {
-        if (!pool.empty()) {
-            hipEvent_t e = pool.back();
-            pool.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        (void)hipEventCreate(&e);
-        return e;
-    }
-};
-Profiler g_prof;
 unsigned long long* g_census = nullptr;  // gsr_census_set: device counters of the census render kernels
-
-struct StageScope {
-    int stage;
-    hipStream_t stream;
-    hipEvent_t a = nullptr;
-    StageScope(int s, hipStream_t st) : stage(s), stream(st) {
-        if ((g_prof.mask >> s) & 1u) {
-            std::lock_guard<std::mutex> lk(g_prof.mu);
-            a = g_prof.get();
-            (void)hipEventRecord(a, stream);
-        }
-    }
-    ~StageScope() {
-        if (a) {
-            std::lock_guard<std::mutex> lk(g_prof.mu);
-            hipEvent_t b = g_prof.get();
-            (void)hipEventRecord(b, stream);
-            g_prof.pending.push_back({stage, a, b});
-        }
-    }
-};
 
 int check_debug(int debug, hipStream_t stream, const char* stage) {
     if (!debug) return GSR_OK;
@@ -528,11 +461,6 @@ struct HostTimer {  // adds the scope's host time to a HostStat
     }
 };
 
-void* call_alloc(gsr_alloc_fn fn, void* ctx, size_t bytes) {
-    if (!fn) return nullptr;
-    return fn(ctx, bytes ? bytes : 1);
-}
-
 }  // namespace
 
 extern "C" {
@@ -563,7 +491,7 @@ int gsr_host_stats(double* values, int n, int reset) {
 }
 
 int gsr_option_set(const char* name, int value) {
-    g_err[0] = 0;
+    clear_error();
     const int i = option_index(name);
     if (i < 0) return fail(GSR_ERR_ARGUMENT, "option_set: unknown option '%s'", name ? name : "(null)");
     const OptionSpec& o = kOptions[i];
@@ -580,7 +508,7 @@ int gsr_option_get(const char* name) {
 }
 
 int gsr_option_set_thread(const char* name, int value) {
-    g_err[0] = 0;
+    clear_error();
     const int i = option_index(name);
     if (i < 0) return fail(GSR_ERR_ARGUMENT, "option_set_thread: unknown option '%s'", name ? name : "(null)");
     const OptionSpec& o = kOptions[i];
@@ -591,7 +519,7 @@ int gsr_option_set_thread(const char* name, int value) {
 }
 
 int gsr_option_clear_thread(const char* name) {
-    g_err[0] = 0;
+    clear_error();
     if (!name) {
         for (int i = 0; i < OPT_COUNT; i++) t_opt[i] = kOptNone;
         return GSR_OK;
@@ -603,237 +531,8 @@ int gsr_option_clear_thread(const char* name) {
 }
 
 int gsr_geom_forget(const void* geom_buffer) {
-    g_err[0] = 0;
+    clear_error();
     geom_forget(geom_buffer);
-    return GSR_OK;
-}
-
-int gsr_fused_ssim_forward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,
-                           float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream) {
-    g_err[0] = 0;
-    if (B < 0 || CH < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARGUMENT, "fused_ssim: negative size");
-    const long long planes = (long long)B * CH;
-    if (planes == 0 || H == 0 || W == 0) return GSR_OK;
-    if (planes > 65535) return fail(GSR_ERR_ARGUMENT, "fused_ssim: B*CH=%lld exceeds 65535 planes", planes);
-    if (!img1 || !img2 || !ssim_map) return fail(GSR_ERR_ARGUMENT, "fused_ssim: null pointer");
-    const int ndm = (dm_dmu1 != nullptr) + (dm_dsigma1_sq != nullptr) + (dm_dsigma12 != nullptr);
-    if (ndm != 0 && ndm != 3) return fail(GSR_ERR_ARGUMENT, "fused_ssim: pass all three derivative maps or none");
-    HIP_TRY(gsr::launch_ssim_fwd((int)planes, H, W, C1, C2, img1, img2, ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
-                                 (hipStream_t)stream),
-            "fused_ssim forward");
-    return GSR_OK;
-}
-
-int gsr_fused_ssim_backward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,
-                            const float* dL_dmap, const float* dm_dmu1, const float* dm_dsigma1_sq,
-                            const float* dm_dsigma12, float* dL_dimg1, void* stream) {
-    (void)C1;  // the derivative maps already carry C1 and C2 (ssim.cu:315-366 does not use them either)
-    (void)C2;
-    g_err[0] = 0;
-    if (B < 0 || CH < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARGUMENT, "fused_ssim: negative size");
-    const long long planes = (long long)B * CH;
-    if (planes == 0 || H == 0 || W == 0) return GSR_OK;
-    if (planes > 65535) return fail(GSR_ERR_ARGUMENT, "fused_ssim: B*CH=%lld exceeds 65535 planes", planes);
-    if (!img1 || !img2 || !dL_dmap || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1)
-        return fail(GSR_ERR_ARGUMENT, "fused_ssim backward: null pointer");
-    HIP_TRY(gsr::launch_ssim_bwd((int)planes, H, W, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1,
-                                 (hipStream_t)stream),
-            "fused_ssim backward");
-    return GSR_OK;
-}
-
-int gsr_knn_mean_dist2(int P, const float* points, float* mean_dists, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
-                       void* stream_) {
-    g_err[0] = 0;
-    hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0) return fail(GSR_ERR_ARGUMENT, "knn: P must be >= 0");
-    if (P == 0) return GSR_OK;
-    if (!points || !mean_dists) return fail(GSR_ERR_ARGUMENT, "knn: null pointer");
-    const size_t bytes = gsr::knn_scratch_bytes(P);
-    void* scratch = call_alloc(scratch_alloc, scratch_ctx, bytes);
-    if (!scratch) return fail(GSR_ERR_ALLOC, "knn: scratch allocation of %zu bytes failed", bytes);
-    HIP_TRY(gsr::launch_knn(P, points, mean_dists, scratch, stream), "knn");
-    // the caller frees the scratch after the call: finish the work first
-    HIP_TRY(hipStreamSynchronize(stream), "knn sync");
-    return GSR_OK;
-}
-
-// ---- SparseGaussianAdam's step (include/gsr_adam.h) -------------------------------
-static_assert(GSR_ADAM_MAX_GROUPS == gsr::kAdamMaxGroups, "group table size");
-
-static int adam_launch(const gsr_adam_group* groups, int n_groups, const unsigned char* visible, int N, float b1,
-                       float b2, void* stream) {
-    using namespace gsr;
-    g_err[0] = 0;
-    if (n_groups < 0 || n_groups > GSR_ADAM_MAX_GROUPS)
-        return fail(GSR_ERR_ARGUMENT, "adam_update: %d parameter groups (0..%d)", n_groups, GSR_ADAM_MAX_GROUPS);
-    if (N < 0) return fail(GSR_ERR_ARGUMENT, "adam_update: N must be >= 0");
-    if (N == 0 || n_groups == 0) return GSR_OK;
-    if (!visible || !groups) return fail(GSR_ERR_ARGUMENT, "adam_update: null pointer");
-    AdamArgs a{};
-    a.vis = visible;
-    a.b1 = b1;
-    a.b2 = b2;
-    uint32_t blocks = 0;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_adam_group& s = groups[k];
-        if (s.M <= 0 || s.numel != (long long)N * s.M)
-            return fail(GSR_ERR_ARGUMENT, "adam_update: group %d has %lld values, expected N*M = %d*%d", k, s.numel, N,
-                        s.M);
-        if (s.numel > 0x7fffffffLL)
-            return fail(GSR_ERR_ARGUMENT, "adam_update: group %d has more than 2^31-1 values", k);
-        if (!s.param || !s.grad || !s.exp_avg || !s.exp_avg_sq)
-            return fail(GSR_ERR_ARGUMENT, "adam_update: group %d has a null parameter/state pointer", k);
-        AdamGroupDev& G = a.grp[a.n_groups++];
-        G.p = s.param; G.g = s.grad; G.m = s.exp_avg; G.v = s.exp_avg_sq;
-        G.n = (uint32_t)s.numel;
-        G.M = (uint32_t)s.M;
-        uint32_t l = 0;
-        while ((1u << l) < G.M) l++;
-        G.shift = 31 + l;
-        G.magic = ((1ull << G.shift) + G.M - 1) / G.M;  // ceil(2^(31+l) / M): exact i / M for i < 2^31
-        G.lr = s.lr;
-        G.eps = s.eps;
-        G.first_block = blocks;
-        G.vec = al16(s.param) && al16(s.grad) && al16(s.exp_avg) && al16(s.exp_avg_sq);
-        blocks += (G.n + kAdamBlockElems - 1) / kAdamBlockElems;
-    }
-    HIP_TRY(launch_adam(a, blocks, (hipStream_t)stream), "adam_update");
-    return GSR_OK;
-}
-
-int gsr_adam_update(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const unsigned char* visible,
-                    float lr, float b1, float b2, float eps, int N, int M, void* stream) {
-    const gsr_adam_group g{param, grad, exp_avg, exp_avg_sq, (long long)N * M, M, lr, eps};
-    return adam_launch(&g, 1, visible, N, b1, b2, stream);
-}
-
-int gsr_adam_update_multi(const gsr_adam_group* groups, int n_groups, const unsigned char* visible, int N, float b1,
-                          float b2, void* stream) {
-    return adam_launch(groups, n_groups, visible, N, b1, b2, stream);
-}
-
-// ---- adaptive density control (include/gsr_densify.h) ------------------------------
-int gsr_densify_stats(int P, const float* viewspace_grad, const int* radii, const unsigned char* visible,
-                      float* grad_accum, float* denom, float* max_radii2D, void* stream) {
-    using namespace gsr;
-    g_err[0] = 0;
-    if (P < 0) return fail(GSR_ERR_ARGUMENT, "densify_stats: P must be >= 0");
-    if (P == 0) return GSR_OK;
-    if (viewspace_grad && (!grad_accum || !denom)) return fail(GSR_ERR_ARGUMENT, "densify_stats: null accumulator");
-    if (!viewspace_grad && !(radii && max_radii2D))
-        return fail(GSR_ERR_ARGUMENT, "densify_stats: nothing to update");
-    if (!radii && !visible) return fail(GSR_ERR_ARGUMENT, "densify_stats: need radii or a visibility mask");
-    HIP_TRY(launch_densify_stats(P, viewspace_grad, radii, visible, grad_accum, denom, max_radii2D,
-                                 (hipStream_t)stream),
-            "densify_stats");
-    return GSR_OK;
-}
-
-unsigned long long gsr_densify_scratch_bytes(int P) { return P > 0 ? gsr::densify_scratch_bytes(P) : 0ull; }
-
-int gsr_densify_plan(int P, const float* grad_accum, const float* denom, const float* opacity, const float* scaling,
-                     const gsr_densify_params* prm, void* scratch, unsigned char* split_mask, long long* counts,
-                     void* stream) {
-    using namespace gsr;
-    g_err[0] = 0;
-    if (!prm || !counts) return fail(GSR_ERR_ARGUMENT, "densify_plan: null params/counts");
-    if (P < 0) return fail(GSR_ERR_ARGUMENT, "densify_plan: P must be >= 0");
-    for (int k = 0; k < GSR_DENSIFY_NCOUNTS; k++) counts[k] = 0;
-    if (P == 0) return GSR_OK;
-    if (!grad_accum || !denom || !opacity || !scaling || !scratch)
-        return fail(GSR_ERR_ARGUMENT, "densify_plan: null pointer");
-    if (prm->split_n < 1 || prm->split_n > 64) return fail(GSR_ERR_ARGUMENT, "densify_plan: split N = %d", prm->split_n);
-    DensifyArgs a{};
-    a.P = P;
-    a.accum = grad_accum; a.denom = denom; a.opacity = opacity; a.scaling = scaling;
-    a.grad_threshold = prm->grad_threshold; a.clone_extent = prm->clone_extent; a.min_opacity = prm->min_opacity;
-    a.big_extent = prm->big_extent; a.split_div = prm->split_div; a.use_screen_size = prm->use_screen_size;
-    a.split_mask = split_mask;
-    densify_carve(scratch, P, a);
-    const hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_densify_plan(a, s), "densify_plan");
-    uint32_t tot[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, a.totals, sizeof(tot), hipMemcpyDeviceToHost, s), "densify_plan counts");
-    HIP_TRY(hipStreamSynchronize(s), "densify_plan sync");
-    counts[GSR_DENSIFY_KEPT] = tot[0];
-    counts[GSR_DENSIFY_CLONES] = tot[1];
-    counts[GSR_DENSIFY_CHILDREN] = tot[2];
-    counts[GSR_DENSIFY_SPLIT] = tot[3];
-    counts[GSR_DENSIFY_TOTAL] = (long long)tot[0] + tot[1] + (long long)prm->split_n * tot[2];
-    if (counts[GSR_DENSIFY_TOTAL] > 0x7fffffffLL)
-        return fail(GSR_ERR_OVERFLOW, "densify_plan: %lld Gaussians after densification", counts[GSR_DENSIFY_TOTAL]);
-    return GSR_OK;
-}
-
-int gsr_densify_apply(int P, const void* scratch, const gsr_densify_group* groups, int n_groups,
-                      const float* rotation, const float* samples, const int* tmp_radii_in, int* tmp_radii_out,
-                      const gsr_densify_params* prm, void* stream) {
-    using namespace gsr;
-    g_err[0] = 0;
-    if (!prm) return fail(GSR_ERR_ARGUMENT, "densify_apply: null params");
-    if (P < 0 || n_groups < 0 || n_groups > GSR_DENSIFY_MAX_GROUPS)
-        return fail(GSR_ERR_ARGUMENT, "densify_apply: P = %d, %d groups (0..%d)", P, n_groups, GSR_DENSIFY_MAX_GROUPS);
-    if (P == 0) return GSR_OK;
-    if (!scratch || (n_groups > 0 && !groups)) return fail(GSR_ERR_ARGUMENT, "densify_apply: null pointer");
-    if ((tmp_radii_in == nullptr) != (tmp_radii_out == nullptr))
-        return fail(GSR_ERR_ARGUMENT, "densify_apply: tmp_radii in and out must both be given or both be null");
-    DensifyArgs d{};
-    densify_carve(const_cast<void*>(scratch), P, d);
-    const hipStream_t s = (hipStream_t)stream;
-    uint32_t tot[4] = {0, 0, 0, 0};  // the plan's totals (a tiny synchronous read; the plan already synchronised)
-    HIP_TRY(hipMemcpyAsync(tot, d.totals, sizeof(tot), hipMemcpyDeviceToHost, s), "densify_apply counts");
-    HIP_TRY(hipStreamSynchronize(s), "densify_apply sync");
-    if ((unsigned long long)tot[0] + tot[1] + (unsigned long long)prm->split_n * tot[2] == 0)
-        return GSR_OK;  // everything pruned: the new arrays are empty
-    if (tot[3] > 0 && tot[2] > 0 && !samples)
-        return fail(GSR_ERR_ARGUMENT, "densify_apply: %u split Gaussians but no samples", tot[3]);
-    auto launch = [&](const void* src, void* dst, const void* sm, const void* sv, void* dm, void* dv, int width,
-                      int role, const char* what) -> int {
-        if (width <= 0) return fail(GSR_ERR_ARGUMENT, "densify_apply: %s width %d", what, width);
-        if ((size_t)P * (size_t)width > 0x7fffffffull)
-            return fail(GSR_ERR_ARGUMENT, "densify_apply: %s has more than 2^31-1 values", what);
-        if (!src || !dst) return fail(GSR_ERR_ARGUMENT, "densify_apply: %s null array", what);
-        if ((sm == nullptr) != (dm == nullptr) || (sv == nullptr) != (dv == nullptr) || (sm == nullptr) != (sv == nullptr))
-            return fail(GSR_ERR_ARGUMENT, "densify_apply: %s Adam state pointers must all be given or all be null",
-                        what);
-        if (role == GSR_DENSIFY_XYZ && (width != 3 || !rotation))
-            return fail(GSR_ERR_ARGUMENT, "densify_apply: the xyz group needs width 3 and the rotations");
-        if (role == GSR_DENSIFY_SCALING && width != 3)
-            return fail(GSR_ERR_ARGUMENT, "densify_apply: the scaling group needs width 3");
-        if (role < GSR_DENSIFY_COPY || role > GSR_DENSIFY_SCALING)
-            return fail(GSR_ERR_ARGUMENT, "densify_apply: %s role %d", what, role);
-        DensifyApplyArgs a{};
-        a.src = (const uint32_t*)src; a.dst = (uint32_t*)dst;
-        a.src_m = (const uint32_t*)sm; a.src_v = (const uint32_t*)sv; a.dst_m = (uint32_t*)dm; a.dst_v = (uint32_t*)dv;
-        a.n = (uint32_t)((size_t)P * width);
-        a.width = (uint32_t)width;
-        uint32_t l = 0;
-        while ((1u << l) < a.width) l++;
-        a.shift = 31 + l;
-        a.magic = ((1ull << a.shift) + a.width - 1) / a.width;  // exact t / width for t < 2^31
-        a.role = role;
-        a.rows = d.rows;
-        a.rotation = rotation;
-        a.samples = samples;
-        a.n_split = tot[3];
-        a.n_children = tot[2];
-        a.split_n = prm->split_n;
-        a.split_div = prm->split_div;
-        HIP_TRY(launch_densify_apply(a, s), "densify_apply");
-        return GSR_OK;
-    };
-    for (int k = 0; k < n_groups; k++) {
-        const gsr_densify_group& g = groups[k];
-        if (int rc = launch(g.src, g.dst, g.src_exp_avg, g.src_exp_avg_sq, g.dst_exp_avg, g.dst_exp_avg_sq, g.width,
-                            g.role, "group"))
-            return rc;
-    }
-    if (tmp_radii_in)
-        if (int rc = launch(tmp_radii_in, tmp_radii_out, nullptr, nullptr, nullptr, nullptr, 1, GSR_DENSIFY_COPY,
-                            "tmp_radii"))
-            return rc;
     return GSR_OK;
 }
 
@@ -888,7 +587,7 @@ const char* gsr_profile_stage_name(int stage) {
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      unsigned char* present, void* stream) {
     (void)projmatrix;  // checkFrustum computes the projection but only tests view-space z
-    g_err[0] = 0;
+    clear_error();
     if (P < 0) return fail(GSR_ERR_ARGUMENT, "mark_visible: P must be >= 0");
     if (P == 0) return GSR_OK;
     if (!means3D || !viewmatrix || !present) return fail(GSR_ERR_ARGUMENT, "mark_visible: null pointer");
@@ -908,7 +607,7 @@ int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_a
                  int* binning_capacity, bool quantized = true) {
     using namespace gsr;
     HostTimer host_time(g_fwd_host);
-    g_err[0] = 0;
+    clear_error();
     hipStream_t stream = (hipStream_t)stream_;
     // every option is read ONCE per call: gsr_option_set may run on another thread, and the launches
     // of one forward (K4's prefix and the redo, the render's part protocol, the work list's segment
@@ -1241,7 +940,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
                   float* view_block = nullptr) {
     using namespace gsr;
     HostTimer host_time(g_bwd_host);
-    g_err[0] = 0;
+    clear_error();
     hipStream_t stream = (hipStream_t)stream_;
     // view_block: screen-space backward only -- the render-gradient sums, flags and camera go
     // into the block (gsr_rasterize_backward_screen) and the per-Gaussian backward is skipped
@@ -1541,77 +1240,6 @@ int gsr_rasterize_backward_dc(int P, int D, int M, int R, const float* backgroun
 
 }  // extern "C"
 
-// ---- multi-GPU view exchange (include/gsr.h) -----------------------------------------
-unsigned long long gsr_view_block_floats(int P) { return P > 0 ? gsr::view_block_floats((size_t)P) : 0ull; }
-
-unsigned long long gsr_view_pack_floats(long long entries) {
-    return gsr::view_pack_floats(entries > 0 ? (size_t)entries : 0);
-}
-
-unsigned long long gsr_view_pack_scratch_bytes(int P) { return P > 0 ? 4ull * ((P + 255) / 256) : 4ull; }
-
-int gsr_view_block_pack_range(int P, int g0, int g1, const float* view_block, float* packed, long long cap,
-                              void* scratch, unsigned int* count, void* stream) {
-    g_err[0] = 0;
-    if (P <= 0 || cap < 0) return fail(GSR_ERR_ARGUMENT, "view_block_pack: P=%d cap=%lld", P, cap);
-    if (g0 < 0 || g1 < g0 || g1 > P) return fail(GSR_ERR_ARGUMENT, "view_block_pack: range [%d, %d) of P=%d", g0, g1, P);
-    if (!view_block || !packed || !scratch) return fail(GSR_ERR_ARGUMENT, "view_block_pack: null pointer");
-    if ((reinterpret_cast<uintptr_t>(view_block) & 15) || (reinterpret_cast<uintptr_t>(packed) & 15))
-        return fail(GSR_ERR_ARGUMENT, "view_block_pack: blocks must be 16-byte aligned");
-    HIP_TRY(gsr::launch_view_pack((uint32_t)P, (uint32_t)g0, (uint32_t)g1, view_block, packed, (unsigned long long)cap,
-                                  reinterpret_cast<uint32_t*>(scratch), count, (hipStream_t)stream),
-            "view_block_pack");
-    return GSR_OK;
-}
-
-int gsr_view_block_pack(int P, const float* view_block, float* packed, long long cap, void* scratch,
-                        unsigned int* count, void* stream) {
-    return gsr_view_block_pack_range(P, 0, P, view_block, packed, cap, scratch, count, stream);
-}
-
-int gsr_view_block_unpack(int P, int n_views, const float* packed, long long packed_floats, float* blocks,
-                          long long cap, void* stream) {
-    g_err[0] = 0;
-    if (P <= 0 || n_views < 0 || cap < 0 || packed_floats < (long long)gsr::view_pack_floats(0))
-        return fail(GSR_ERR_ARGUMENT, "view_block_unpack: P=%d views=%d packed_floats=%lld cap=%lld", P, n_views,
-                    packed_floats, cap);
-    if ((size_t)packed_floats < gsr::view_pack_floats((size_t)cap))
-        return fail(GSR_ERR_ARGUMENT, "view_block_unpack: %lld floats per packed block cannot hold %lld entries",
-                    packed_floats, cap);
-    if (n_views > 0 && (!packed || !blocks)) return fail(GSR_ERR_ARGUMENT, "view_block_unpack: null pointer");
-    if ((reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(blocks) & 15) || (packed_floats & 3))
-        return fail(GSR_ERR_ARGUMENT, "view_block_unpack: blocks must be 16-byte aligned");
-    HIP_TRY(gsr::launch_view_unpack((uint32_t)P, n_views, packed, (unsigned long long)packed_floats, blocks,
-                                    (unsigned long long)cap, (hipStream_t)stream),
-            "view_block_unpack");
-    return GSR_OK;
-}
-
-int gsr_view_block_index(int P, int n_views, const float* packed, long long packed_floats, unsigned int* flags,
-                         long long cap, void* stream) {
-    return gsr_view_block_index_range(P, 0, P, n_views, packed, packed_floats, flags, cap, stream);
-}
-
-int gsr_view_block_index_range(int P, int g0, int g1, int n_views, const float* packed, long long packed_floats,
-                               unsigned int* flags, long long cap, void* stream) {
-    g_err[0] = 0;
-    if (g0 < 0 || g1 < g0 || g1 > P) return fail(GSR_ERR_ARGUMENT, "view_block_index: range [%d, %d) of P=%d", g0, g1, P);
-    if (P <= 0 || n_views < 0 || cap < 0 || packed_floats < (long long)gsr::view_pack_floats(0))
-        return fail(GSR_ERR_ARGUMENT, "view_block_index: P=%d views=%d packed_floats=%lld cap=%lld", P, n_views,
-                    packed_floats, cap);
-    if ((size_t)packed_floats < gsr::view_pack_floats((size_t)cap))
-        return fail(GSR_ERR_ARGUMENT, "view_block_index: %lld floats per packed block cannot hold %lld entries",
-                    packed_floats, cap);
-    if (cap >= (1ll << 28)) return fail(GSR_ERR_ARGUMENT, "view_block_index: %lld entries exceed 2^28", cap);
-    if (n_views > 0 && (!packed || !flags)) return fail(GSR_ERR_ARGUMENT, "view_block_index: null pointer");
-    if ((reinterpret_cast<uintptr_t>(packed) & 15) || (packed_floats & 3))
-        return fail(GSR_ERR_ARGUMENT, "view_block_index: packed blocks must be 16-byte aligned");
-    HIP_TRY(gsr::launch_view_index((uint32_t)P, (uint32_t)g0, (uint32_t)g1, n_views, packed,
-                                   (unsigned long long)packed_floats, flags, (unsigned long long)cap, (hipStream_t)stream),
-            "view_block_index");
-    return GSR_OK;
-}
-
 int gsr_rasterize_backward_screen(int P, int D, int M, int R, const float* background, int width, int height,
                                   const float* means3D, const float* dc, const float* shs, const float* opacities,
                                   const float* scales, float scale_modifier, const float* rotations,
@@ -1636,7 +1264,7 @@ int gsr_debug_forward_state(int P, int width, int height, int R, int binning_cap
                             unsigned int* ranges, unsigned int* point_list, unsigned int* n_contrib, float* final_T,
                             void* stream_) {
     using namespace gsr;
-    g_err[0] = 0;
+    clear_error();
     hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0 || R < 0 || width <= 0 || height <= 0)
         return fail(GSR_ERR_ARGUMENT, "debug_forward_state: invalid sizes P=%d R=%d W=%d H=%d", P, R, width, height);
@@ -1673,7 +1301,7 @@ int gsr_debug_forward_state(int P, int width, int height, int R, int binning_cap
 int gsr_debug_sort_state(int P, int width, int height, const void* geom_buffer, unsigned int* sorted_len,
                          unsigned int* redo_count, void* stream_) {
     using namespace gsr;
-    g_err[0] = 0;
+    clear_error();
     hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0 || width <= 0 || height <= 0 || !geom_buffer)
         return fail(GSR_ERR_ARGUMENT, "debug_sort_state: invalid sizes or no geometry buffer");
@@ -1692,7 +1320,7 @@ int gsr_debug_sort_state(int P, int width, int height, const void* geom_buffer, 
 int gsr_debug_near_state(int P, int width, int height, const void* geom_buffer, unsigned int* zcut,
                          unsigned int* near_ranges, void* stream_) {
     using namespace gsr;
-    g_err[0] = 0;
+    clear_error();
     hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0 || width <= 0 || height <= 0 || !geom_buffer)
         return fail(GSR_ERR_ARGUMENT, "debug_near_state: invalid sizes or no geometry buffer");
@@ -1705,109 +1333,4 @@ int gsr_debug_near_state(int P, int width, int height, const void* geom_buffer, 
         HIP_TRY(hipMemcpyAsync(near_ranges, geom.sranges, sizeof(uint2) * gx * gy, hipMemcpyDeviceToDevice, stream),
                 "debug_near_state sranges");
     return GSR_OK;
-}
-
-namespace {
-int backward_views_impl(int P, int D, int M, const float* means3D, const float* dc, const float* shs,
-                        const float* opacities, const float* scales, const float* rotations, float scale_modifier,
-                        int n_views, const float* blocks, long long block_floats, const unsigned int* flags,
-                        const unsigned int* live, const unsigned int* live_count, float* dL_dmean3D, float* dL_ddc,
-                        float* dL_dsh, float* dL_dopacity, float* dL_dscale, float* dL_drot, void* stream) {
-    using namespace gsr;
-    g_err[0] = 0;
-    if (P < 0 || n_views < 0) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: P=%d views=%d", P, n_views);
-    if (P == 0) return GSR_OK;
-    if (!flags && (size_t)block_floats != view_block_floats((size_t)P))
-        return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: block of %lld floats, expected %zu", block_floats,
-                    view_block_floats((size_t)P));
-    if (flags && (block_floats < (long long)view_pack_floats(0) || (block_floats & 3) ||
-                  (reinterpret_cast<uintptr_t>(blocks) & 15)))
-        return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: packed blocks of %lld floats (16-byte aligned)",
-                    block_floats);
-    if (!means3D || !opacities || !scales || !rotations || (n_views > 0 && !blocks) || !dL_dmean3D || !dL_dopacity ||
-        !dL_dscale || !dL_drot)
-        return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: null pointer");
-    if (D < 0 || D > 3) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: SH degree %d", D);
-    if (dc && M > 0 && !shs) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: rest SH without shs");
-    if ((shs && !dL_dsh) || (dc && !dL_ddc)) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: missing SH outputs");
-    if (!dc && !shs) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: needs SH (precomputed colours are per view)");
-    if ((D + 1) * (D + 1) > (dc ? M + 1 : M))  // as the forward (forward_impl): never read past a row
-        return fail(GSR_ERR_ARGUMENT, "gauss_backward_views: SH degree %d needs %d coefficients, got %d", D,
-                    (D + 1) * (D + 1), dc ? M + 1 : M);
-    ViewsBwdArgs a{};
-    a.P = P; a.D = D; a.M = dc ? M + 1 : M;
-    a.means3D = means3D; a.shs = (dc && M == 0) ? nullptr : shs; a.dc = dc; a.opacities = opacities; a.scales = scales;
-    a.rotations = rotations; a.scale_modifier = scale_modifier; a.n_views = n_views; a.blocks = blocks;
-    a.block_floats = (size_t)block_floats;
-    a.flags = flags;
-    a.live = live;
-    a.live_count = live_count;
-    a.live_cap = live_list_cap((uint32_t)P);
-    a.dL_dmean3D = dL_dmean3D; a.dL_dsh = a.shs ? dL_dsh : nullptr; a.dL_ddc = dc ? dL_ddc : nullptr;
-    a.dL_dopacity = dL_dopacity; a.dL_dscale = dL_dscale; a.dL_drot = dL_drot;
-    {
-        StageScope sc(ST_GAUSS_BWD, (hipStream_t)stream);
-        HIP_TRY(launch_gauss_bwd_views(a, (hipStream_t)stream), "gauss_backward_views");
-    }
-    return GSR_OK;
-}
-}  // namespace
-
-int gsr_gauss_backward_views(int P, int D, int M, const float* means3D, const float* dc, const float* shs,
-                             const float* opacities, const float* scales, const float* rotations, float scale_modifier,
-                             int n_views, const float* blocks, long long block_floats, float* dL_dmean3D,
-                             float* dL_ddc, float* dL_dsh, float* dL_dopacity, float* dL_dscale, float* dL_drot,
-                             void* stream) {
-    return backward_views_impl(P, D, M, means3D, dc, shs, opacities, scales, rotations, scale_modifier, n_views,
-                               blocks, block_floats, nullptr, nullptr, nullptr, dL_dmean3D, dL_ddc, dL_dsh, dL_dopacity,
-                               dL_dscale, dL_drot, stream);
-}
-
-int gsr_gauss_backward_views_packed(int P, int D, int M, const float* means3D, const float* dc, const float* shs,
-                                    const float* opacities, const float* scales, const float* rotations,
-                                    float scale_modifier, int n_views, const float* packed, long long packed_floats,
-                                    const unsigned int* flags, float* dL_dmean3D, float* dL_ddc, float* dL_dsh,
-                                    float* dL_dopacity, float* dL_dscale, float* dL_drot, void* stream) {
-    if (n_views > 0 && !flags) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views_packed: null flags");
-    return backward_views_impl(P, D, M, means3D, dc, shs, opacities, scales, rotations, scale_modifier, n_views,
-                               packed, packed_floats, flags, nullptr, nullptr, dL_dmean3D, dL_ddc, dL_dsh, dL_dopacity,
-                               dL_dscale, dL_drot, stream);
-}
-
-unsigned long long gsr_views_live_floats(int P) {
-    return P > 0 ? (unsigned long long)gsr::kLiveShards * gsr::live_list_cap((uint32_t)P) +
-                       (unsigned long long)gsr::kLiveShards * gsr::kLiveCntStride
-                 : 0ull;
-}
-
-int gsr_views_live_list_range(int P, int g0, int g1, int n_views, const unsigned int* flags, unsigned int* live,
-                              void* stream) {
-    g_err[0] = 0;
-    if (P < 0 || n_views < 0) return fail(GSR_ERR_ARGUMENT, "views_live_list: P=%d views=%d", P, n_views);
-    if (g0 < 0 || g1 < g0 || g1 > P) return fail(GSR_ERR_ARGUMENT, "views_live_list: range [%d, %d) of P=%d", g0, g1, P);
-    if (P == 0) return GSR_OK;
-    if (!live || (n_views > 0 && !flags)) return fail(GSR_ERR_ARGUMENT, "views_live_list: null pointer");
-    unsigned int* count = live + (size_t)gsr::kLiveShards * gsr::live_list_cap((uint32_t)P);
-    HIP_TRY(gsr::launch_views_live((uint32_t)P, (uint32_t)g0, (uint32_t)g1, n_views, flags, live, count,
-                                   (hipStream_t)stream),
-            "views_live_list");
-    return GSR_OK;
-}
-
-int gsr_views_live_list(int P, int n_views, const unsigned int* flags, unsigned int* live, void* stream) {
-    return gsr_views_live_list_range(P, 0, P, n_views, flags, live, stream);
-}
-
-int gsr_gauss_backward_views_live(int P, int D, int M, const float* means3D, const float* dc, const float* shs,
-                                  const float* opacities, const float* scales, const float* rotations,
-                                  float scale_modifier, int n_views, const float* packed, long long packed_floats,
-                                  const unsigned int* flags, const unsigned int* live, float* dL_dmean3D,
-                                  float* dL_ddc, float* dL_dsh, float* dL_dopacity, float* dL_dscale, float* dL_drot,
-                                  void* stream) {
-    if (n_views > 0 && (!flags || !live)) return fail(GSR_ERR_ARGUMENT, "gauss_backward_views_live: null list");
-    const unsigned int* count = live ? live + (size_t)gsr::kLiveShards * gsr::live_list_cap((uint32_t)(P > 0 ? P : 0))
-                                     : nullptr;
-    return backward_views_impl(P, D, M, means3D, dc, shs, opacities, scales, rotations, scale_modifier, n_views,
-                               packed, packed_floats, flags, live, count, dL_dmean3D, dL_ddc, dL_dsh, dL_dopacity,
-                               dL_dscale, dL_drot, stream);
 }

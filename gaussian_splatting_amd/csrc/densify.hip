@@ -17,9 +17,47 @@
 // plan, scan and index are HBM-light (24 B read, 17 B written per Gaussian); apply moves each
 // parameter and moment once (HBM-bound).  No atomics: the output order is the reference's
 // exactly and the result is bitwise reproducible.
+// The C entry points (include/gsr_densify.h) are at the end of the file.
+#include "../../include/gsr_densify.h"
+#include "host.h"
 #include "kernels.h"
 
 namespace gsr {
+
+struct DensifyArgs {
+    int P;
+    const float* accum;
+    const float* denom;
+    const float* opacity;
+    const float* scaling;
+    float grad_threshold, clone_extent, min_opacity, big_extent, split_div;
+    int use_screen_size;
+    uint8_t* split_mask;  // may be null
+    // scratch (densify_carve)
+    int4* rows;           // [P] kept row, clone row, first child row, split rank (-1: none)
+    uint8_t* flags;       // [P]
+    uint32_t* blk;        // [blocks][4] counts, then exclusive offsets
+    uint32_t* totals;     // [4] kept, clones, children per copy, splits
+};
+struct DensifyApplyArgs {
+    const uint32_t* src;
+    uint32_t* dst;
+    const uint32_t* src_m;
+    const uint32_t* src_v;
+    uint32_t* dst_m;  // null: the group has no Adam state
+    uint32_t* dst_v;
+    uint32_t n;       // P * width
+    uint32_t width;
+    unsigned long long magic;  // t / width == (t * magic) >> shift for t < 2^31
+    uint32_t shift;
+    int role;
+    const int4* rows;
+    const float* rotation;
+    const float* samples;
+    uint32_t n_split, n_children;
+    int split_n;
+    float split_div;
+};
 
 constexpr int kDenThreads = 256;
 constexpr int kDenWaves = kDenThreads / 64;
@@ -239,13 +277,13 @@ __global__ void __launch_bounds__(kDenThreads) densify_apply_kernel(DensifyApply
 }
 
 // ---- launchers ----------------------------------------------------------------------
-size_t densify_scratch_bytes(int P) {
+static size_t densify_scratch_bytes(int P) {
     const size_t nblk = ((size_t)P + kDenThreads - 1) / kDenThreads;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     return al((size_t)P * sizeof(int4)) + al((size_t)P) + al(nblk * 4 * sizeof(uint32_t)) + al(4 * sizeof(uint32_t));
 }
 
-void densify_carve(void* scratch, int P, DensifyArgs& a) {
+static void densify_carve(void* scratch, int P, DensifyArgs& a) {
     const size_t nblk = ((size_t)P + kDenThreads - 1) / kDenThreads;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     char* p = (char*)scratch;
@@ -258,15 +296,15 @@ void densify_carve(void* scratch, int P, DensifyArgs& a) {
     a.totals = (uint32_t*)p;
 }
 
-hipError_t launch_densify_stats(int P, const float* vgrad, const int* radii, const uint8_t* visible, float* accum,
-                                float* denom, float* max_r, hipStream_t stream) {
+static hipError_t launch_densify_stats(int P, const float* vgrad, const int* radii, const uint8_t* visible,
+                                       float* accum, float* denom, float* max_r, hipStream_t stream) {
     if (P <= 0) return hipSuccess;
     hipLaunchKernelGGL(densify_stats_kernel, dim3((P + kDenThreads - 1) / kDenThreads), dim3(kDenThreads), 0, stream,
                        P, vgrad, radii, visible, accum, denom, max_r);
     return hipGetLastError();
 }
 
-hipError_t launch_densify_plan(const DensifyArgs& a, hipStream_t stream) {
+static hipError_t launch_densify_plan(const DensifyArgs& a, hipStream_t stream) {
     if (a.P <= 0) return hipSuccess;
     const uint32_t nblk = (uint32_t)((a.P + kDenThreads - 1) / kDenThreads);
     hipLaunchKernelGGL(densify_plan_kernel, dim3(nblk), dim3(kDenThreads), 0, stream, a);
@@ -275,7 +313,7 @@ hipError_t launch_densify_plan(const DensifyArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_densify_apply(const DensifyApplyArgs& a, hipStream_t stream) {
+static hipError_t launch_densify_apply(const DensifyApplyArgs& a, hipStream_t stream) {
     if (a.n == 0) return hipSuccess;
     hipLaunchKernelGGL(densify_apply_kernel, dim3((a.n + kDenThreads - 1) / kDenThreads), dim3(kDenThreads), 0,
                        stream, a);
@@ -283,3 +321,130 @@ hipError_t launch_densify_apply(const DensifyApplyArgs& a, hipStream_t stream) {
 }
 
 }  // namespace gsr
+
+// ---- C entry points (include/gsr_densify.h) ----------------------------------------
+extern "C" {
+
+int gsr_densify_stats(int P, const float* viewspace_grad, const int* radii, const unsigned char* visible,
+                      float* grad_accum, float* denom, float* max_radii2D, void* stream) {
+    using namespace gsr;
+    clear_error();
+    if (P < 0) return fail(GSR_ERR_ARGUMENT, "densify_stats: P must be >= 0");
+    if (P == 0) return GSR_OK;
+    if (viewspace_grad && (!grad_accum || !denom)) return fail(GSR_ERR_ARGUMENT, "densify_stats: null accumulator");
+    if (!viewspace_grad && !(radii && max_radii2D))
+        return fail(GSR_ERR_ARGUMENT, "densify_stats: nothing to update");
+    if (!radii && !visible) return fail(GSR_ERR_ARGUMENT, "densify_stats: need radii or a visibility mask");
+    HIP_TRY(launch_densify_stats(P, viewspace_grad, radii, visible, grad_accum, denom, max_radii2D,
+                                 (hipStream_t)stream),
+            "densify_stats");
+    return GSR_OK;
+}
+
+unsigned long long gsr_densify_scratch_bytes(int P) { return P > 0 ? gsr::densify_scratch_bytes(P) : 0ull; }
+
+int gsr_densify_plan(int P, const float* grad_accum, const float* denom, const float* opacity, const float* scaling,
+                     const gsr_densify_params* prm, void* scratch, unsigned char* split_mask, long long* counts,
+                     void* stream) {
+    using namespace gsr;
+    clear_error();
+    if (!prm || !counts) return fail(GSR_ERR_ARGUMENT, "densify_plan: null params/counts");
+    if (P < 0) return fail(GSR_ERR_ARGUMENT, "densify_plan: P must be >= 0");
+    for (int k = 0; k < GSR_DENSIFY_NCOUNTS; k++) counts[k] = 0;
+    if (P == 0) return GSR_OK;
+    if (!grad_accum || !denom || !opacity || !scaling || !scratch)
+        return fail(GSR_ERR_ARGUMENT, "densify_plan: null pointer");
+    if (prm->split_n < 1 || prm->split_n > 64) return fail(GSR_ERR_ARGUMENT, "densify_plan: split N = %d", prm->split_n);
+    DensifyArgs a{};
+    a.P = P;
+    a.accum = grad_accum; a.denom = denom; a.opacity = opacity; a.scaling = scaling;
+    a.grad_threshold = prm->grad_threshold; a.clone_extent = prm->clone_extent; a.min_opacity = prm->min_opacity;
+    a.big_extent = prm->big_extent; a.split_div = prm->split_div; a.use_screen_size = prm->use_screen_size;
+    a.split_mask = split_mask;
+    densify_carve(scratch, P, a);
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_densify_plan(a, s), "densify_plan");
+    uint32_t tot[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(tot, a.totals, sizeof(tot), hipMemcpyDeviceToHost, s), "densify_plan counts");
+    HIP_TRY(hipStreamSynchronize(s), "densify_plan sync");
+    counts[GSR_DENSIFY_KEPT] = tot[0];
+    counts[GSR_DENSIFY_CLONES] = tot[1];
+    counts[GSR_DENSIFY_CHILDREN] = tot[2];
+    counts[GSR_DENSIFY_SPLIT] = tot[3];
+    counts[GSR_DENSIFY_TOTAL] = (long long)tot[0] + tot[1] + (long long)prm->split_n * tot[2];
+    if (counts[GSR_DENSIFY_TOTAL] > 0x7fffffffLL)
+        return fail(GSR_ERR_OVERFLOW, "densify_plan: %lld Gaussians after densification", counts[GSR_DENSIFY_TOTAL]);
+    return GSR_OK;
+}
+
+int gsr_densify_apply(int P, const void* scratch, const gsr_densify_group* groups, int n_groups,
+                      const float* rotation, const float* samples, const int* tmp_radii_in, int* tmp_radii_out,
+                      const gsr_densify_params* prm, void* stream) {
+    using namespace gsr;
+    clear_error();
+    if (!prm) return fail(GSR_ERR_ARGUMENT, "densify_apply: null params");
+    if (P < 0 || n_groups < 0 || n_groups > GSR_DENSIFY_MAX_GROUPS)
+        return fail(GSR_ERR_ARGUMENT, "densify_apply: P = %d, %d groups (0..%d)", P, n_groups, GSR_DENSIFY_MAX_GROUPS);
+    if (P == 0) return GSR_OK;
+    if (!scratch || (n_groups > 0 && !groups)) return fail(GSR_ERR_ARGUMENT, "densify_apply: null pointer");
+    if ((tmp_radii_in == nullptr) != (tmp_radii_out == nullptr))
+        return fail(GSR_ERR_ARGUMENT, "densify_apply: tmp_radii in and out must both be given or both be null");
+    DensifyArgs d{};
+    densify_carve(const_cast<void*>(scratch), P, d);
+    const hipStream_t s = (hipStream_t)stream;
+    uint32_t tot[4] = {0, 0, 0, 0};  // the plan's totals (a tiny synchronous read; the plan already synchronised)
+    HIP_TRY(hipMemcpyAsync(tot, d.totals, sizeof(tot), hipMemcpyDeviceToHost, s), "densify_apply counts");
+    HIP_TRY(hipStreamSynchronize(s), "densify_apply sync");
+    if ((unsigned long long)tot[0] + tot[1] + (unsigned long long)prm->split_n * tot[2] == 0)
+        return GSR_OK;  // everything pruned: the new arrays are empty
+    if (tot[3] > 0 && tot[2] > 0 && !samples)
+        return fail(GSR_ERR_ARGUMENT, "densify_apply: %u split Gaussians but no samples", tot[3]);
+    auto launch = [&](const void* src, void* dst, const void* sm, const void* sv, void* dm, void* dv, int width,
+                      int role, const char* what) -> int {
+        if (width <= 0) return fail(GSR_ERR_ARGUMENT, "densify_apply: %s width %d", what, width);
+        if ((size_t)P * (size_t)width > 0x7fffffffull)
+            return fail(GSR_ERR_ARGUMENT, "densify_apply: %s has more than 2^31-1 values", what);
+        if (!src || !dst) return fail(GSR_ERR_ARGUMENT, "densify_apply: %s null array", what);
+        if ((sm == nullptr) != (dm == nullptr) || (sv == nullptr) != (dv == nullptr) || (sm == nullptr) != (sv == nullptr))
+            return fail(GSR_ERR_ARGUMENT, "densify_apply: %s Adam state pointers must all be given or all be null",
+                        what);
+        if (role == GSR_DENSIFY_XYZ && (width != 3 || !rotation))
+            return fail(GSR_ERR_ARGUMENT, "densify_apply: the xyz group needs width 3 and the rotations");
+        if (role == GSR_DENSIFY_SCALING && width != 3)
+            return fail(GSR_ERR_ARGUMENT, "densify_apply: the scaling group needs width 3");
+        if (role < GSR_DENSIFY_COPY || role > GSR_DENSIFY_SCALING)
+            return fail(GSR_ERR_ARGUMENT, "densify_apply: %s role %d", what, role);
+        DensifyApplyArgs a{};
+        a.src = (const uint32_t*)src; a.dst = (uint32_t*)dst;
+        a.src_m = (const uint32_t*)sm; a.src_v = (const uint32_t*)sv; a.dst_m = (uint32_t*)dm; a.dst_v = (uint32_t*)dv;
+        a.n = (uint32_t)((size_t)P * width);
+        a.width = (uint32_t)width;
+        uint32_t l = 0;
+        while ((1u << l) < a.width) l++;
+        a.shift = 31 + l;
+        a.magic = ((1ull << a.shift) + a.width - 1) / a.width;  // exact t / width for t < 2^31
+        a.role = role;
+        a.rows = d.rows;
+        a.rotation = rotation;
+        a.samples = samples;
+        a.n_split = tot[3];
+        a.n_children = tot[2];
+        a.split_n = prm->split_n;
+        a.split_div = prm->split_div;
+        HIP_TRY(launch_densify_apply(a, s), "densify_apply");
+        return GSR_OK;
+    };
+    for (int k = 0; k < n_groups; k++) {
+        const gsr_densify_group& g = groups[k];
+        if (int rc = launch(g.src, g.dst, g.src_exp_avg, g.src_exp_avg_sq, g.dst_exp_avg, g.dst_exp_avg_sq, g.width,
+                            g.role, "group"))
+            return rc;
+    }
+    if (tmp_radii_in)
+        if (int rc = launch(tmp_radii_in, tmp_radii_out, nullptr, nullptr, nullptr, nullptr, 1, GSR_DENSIFY_COPY,
+                            "tmp_radii"))
+            return rc;
+    return GSR_OK;
+}
+
+}  // extern "C"

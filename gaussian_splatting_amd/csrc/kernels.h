@@ -1,8 +1,9 @@
-// kernels.h -- launch arguments and entry points shared by the .hip translation units.
+// kernels.h -- the rasterizer's launch arguments and the launchers that cross translation units.
+// (The other components each keep their argument structs and launchers in their own file, beside their C entry
+// points.)
 #pragma once
 
 #include "gsr_common.h"
-#include "../../include/gsr_densify.h"
 
 namespace gsr {
 
@@ -379,74 +380,6 @@ __device__ __forceinline__ void sh_gather_out(const ShGradAddr& ga, int g, int r
 // SH path of preprocess / gauss_bwd: per-lane global loads, or LDS staging of either layout
 enum ShMode { kShGlobal = 0, kShLdsCombined = 1, kShLdsSplit = 2 };
 
-// ---- sparse Adam (adam.hip) --------------------------------------------------------
-constexpr int kAdamMaxGroups = 8;  // GSR_ADAM_MAX_GROUPS
-struct AdamGroupDev {
-    float* p;
-    const float* g;
-    float* m;
-    float* v;
-    uint32_t n;                // N * M
-    uint32_t M;
-    unsigned long long magic;  // i / M == (i * magic) >> shift for i < 2^31
-    uint32_t shift;
-    float lr, eps;
-    uint32_t first_block;      // first workgroup of this group
-    int vec;                   // all four arrays 16-byte aligned
-};
-struct AdamArgs {
-    AdamGroupDev grp[kAdamMaxGroups];
-    int n_groups;
-    const uint8_t* vis;
-    float b1, b2;
-};
-constexpr int kAdamThreads = 256;
-constexpr int kAdamUnroll = 2;  // float4s per thread
-constexpr uint32_t kAdamBlockElems = kAdamThreads * kAdamUnroll * 4;
-hipError_t launch_adam(const AdamArgs& a, uint32_t blocks, hipStream_t stream);
-
-// ---- adaptive density control (densify.hip) ------------------------------------------
-struct DensifyArgs {
-    int P;
-    const float* accum;
-    const float* denom;
-    const float* opacity;
-    const float* scaling;
-    float grad_threshold, clone_extent, min_opacity, big_extent, split_div;
-    int use_screen_size;
-    uint8_t* split_mask;  // may be null
-    // scratch (densify_carve)
-    int4* rows;           // [P] kept row, clone row, first child row, split rank (-1: none)
-    uint8_t* flags;       // [P]
-    uint32_t* blk;        // [blocks][4] counts, then exclusive offsets
-    uint32_t* totals;     // [4] kept, clones, children per copy, splits
-};
-struct DensifyApplyArgs {
-    const uint32_t* src;
-    uint32_t* dst;
-    const uint32_t* src_m;
-    const uint32_t* src_v;
-    uint32_t* dst_m;  // null: the group has no Adam state
-    uint32_t* dst_v;
-    uint32_t n;       // P * width
-    uint32_t width;
-    unsigned long long magic;  // t / width == (t * magic) >> shift for t < 2^31
-    uint32_t shift;
-    int role;
-    const int4* rows;
-    const float* rotation;
-    const float* samples;
-    uint32_t n_split, n_children;
-    int split_n;
-    float split_div;
-};
-size_t densify_scratch_bytes(int P);
-void densify_carve(void* scratch, int P, DensifyArgs& a);
-hipError_t launch_densify_stats(int P, const float* vgrad, const int* radii, const uint8_t* visible, float* accum,
-                                float* denom, float* max_r, hipStream_t stream);
-hipError_t launch_densify_plan(const DensifyArgs& a, hipStream_t stream);
-hipError_t launch_densify_apply(const DensifyApplyArgs& a, hipStream_t stream);
-
 // preprocess.hip
 hipError_t launch_preprocess(const PreprocessArgs& a, hipStream_t stream);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* view, bool* present, hipStream_t stream);
@@ -505,67 +438,19 @@ hipError_t launch_render_bwd(const RenderBwdArgs& a, size_t max_units, hipStream
 size_t bwd_max_units(size_t R, uint32_t tiles, int seg_ck);
 // Longest reachable prefix K4 sorts ("sort_prefix" option range; binning.hip kPrefixBuf holds twice it).
 constexpr uint32_t kSortPrefixMax = 1024;
-// knn.hip
-size_t knn_scratch_bytes(int P);
-hipError_t launch_knn(int P, const float* pts, float* out, void* scratch, hipStream_t stream);
-// ssim.hip
-hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const float* img1, const float* img2,
-                           float* map, float* dm_dmu1, float* dm_ds11, float* dm_ds12, hipStream_t stream);
-hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const float* img2, const float* dL_dmap,
-                           const float* dm_dmu1, const float* dm_ds11, const float* dm_ds12, float* dL_dimg1,
-                           hipStream_t stream);
 // backward.hip
 hipError_t launch_gauss_reduce(int P, const GeomState& g, const GradRecs& recs, const GradRecs& sums,
                                uint32_t* flags, const int* radii, uint32_t* live, uint32_t* live_count,
                                hipStream_t stream);
+hipError_t launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t stream);
+// views.hip (the two launchers the screen-space backward of api.hip's backward_impl fills a view block with)
 // atomic screen-space backward: the view block's dense sums (a touched Gaussian's row, zeroed after; zeros
 // otherwise) and flag words (visible, SH clamp bits) from the touched bits (re-zeroed) -- gauss_reduce's view
 // block output without records
 hipError_t launch_gauss_live_views(int P, uint32_t* touched, float4* acc, const int* radii, const uint8_t* clamped,
                                    const GradRecs& sums, uint32_t* flags, hipStream_t stream);
-// multi-view backward over gathered view blocks (backward.hip section 4)
-struct ViewsBwdArgs {
-    int P, D, M;
-    const float* means3D;
-    const float* shs;
-    const float* dc;
-    const float* opacities;
-    const float* scales;
-    const float* rotations;
-    float scale_modifier;
-    int n_views;
-    const float* blocks;  // [n_views][block_floats]: view blocks, or packed blocks when `flags` is set
-    size_t block_floats;
-    // Packed mode (gsr_view_block_index): the flag word of Gaussian g in view v is flags[v * P + g],
-    // its entry index in view v's packed block << 4 | the block's flag bits; the sums are read from
-    // that packed entry, the camera from the packed block's header.  Null: dense view blocks.
-    const uint32_t* flags;
-    // with flags: the live list of Gaussians some view flags (launch_views_live), or null; with it
-    // the kernel runs a lane per listed Gaussian and the outputs must be zero beforehand
-    const uint32_t* live;
-    const uint32_t* live_count;
-    uint32_t live_cap;
-    float* dL_dmean3D;
-    float* dL_dsh;
-    float* dL_ddc;
-    float* dL_dopacity;
-    float* dL_dscale;
-    float* dL_drot;
-};
-hipError_t launch_gauss_bwd_views(const ViewsBwdArgs& a, hipStream_t stream);
-// (g0, g1): the Gaussian range of one chunk of a chunked exchange; (0, P) for the whole block
-hipError_t launch_view_pack(uint32_t P, uint32_t g0, uint32_t g1, const float* block, float* packed,
-                            unsigned long long cap, uint32_t* scratch, uint32_t* count, hipStream_t stream);
-hipError_t launch_views_live(uint32_t P, uint32_t g0, uint32_t g1, int n_views, const uint32_t* flags, uint32_t* live,
-                             uint32_t* live_count, hipStream_t stream);
-hipError_t launch_view_index(uint32_t P, uint32_t g0, uint32_t g1, int n_views, const float* packed,
-                             unsigned long long packed_floats, uint32_t* flags, unsigned long long cap,
-                             hipStream_t stream);
-hipError_t launch_view_unpack(uint32_t P, int n_views, const float* packed, unsigned long long packed_floats,
-                              float* blocks, unsigned long long cap, hipStream_t stream);
 hipError_t launch_view_header(float* blk, const float* view, const float* proj, const float* campos, float tan_fovx,
                               float tan_fovy, float focal_x, float focal_y, int antialiasing, int have_invdepth,
                               hipStream_t stream);
-hipError_t launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t stream);
 
 }  // namespace gsr

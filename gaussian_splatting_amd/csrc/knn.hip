@@ -21,11 +21,14 @@
 // The per-lane candidate test and update are the reference's (strict '>' insertion,
 // simple_knn.cu:121-134), and every candidate whose distance could enter the best
 // three is visited, so the result is the exact 3-NN mean whatever the traversal order.
+// The C entry point (include/gsr_knn.h) is at the end of the file.
 #include <cfloat>
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "../../include/gsr_knn.h"
+#include "host.h"
 #include "kernels.h"
 
 namespace gsr {
@@ -241,7 +244,7 @@ KnnCarve carve_knn(char* base, int P, size_t temp_bytes, size_t* total) {
 }
 }  // namespace
 
-size_t knn_scratch_bytes(int P) {
+static size_t knn_scratch_bytes(int P) {
     size_t temp = 0;
     (void)rocprim::radix_sort_pairs(nullptr, temp, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
                                     (uint32_t*)nullptr, (size_t)P, 0, 30);
@@ -250,7 +253,7 @@ size_t knn_scratch_bytes(int P) {
     return total;
 }
 
-hipError_t launch_knn(int P, const float* pts, float* out, void* scratch, hipStream_t stream) {
+static hipError_t launch_knn(int P, const float* pts, float* out, void* scratch, hipStream_t stream) {
     if (P <= 0) return hipSuccess;
     size_t temp = 0, total = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, temp, (uint32_t*)nullptr, (uint32_t*)nullptr,
@@ -272,3 +275,25 @@ hipError_t launch_knn(int P, const float* pts, float* out, void* scratch, hipStr
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_knn_mean_dist2(int P, const float* points, float* mean_dists, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                       void* stream_) {
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0) return fail(GSR_ERR_ARGUMENT, "knn: P must be >= 0");
+    if (P == 0) return GSR_OK;
+    if (!points || !mean_dists) return fail(GSR_ERR_ARGUMENT, "knn: null pointer");
+    const size_t bytes = gsr::knn_scratch_bytes(P);
+    void* scratch = call_alloc(scratch_alloc, scratch_ctx, bytes);
+    if (!scratch) return fail(GSR_ERR_ALLOC, "knn: scratch allocation of %zu bytes failed", bytes);
+    HIP_TRY(gsr::launch_knn(P, points, mean_dists, scratch, stream), "knn");
+    // the caller frees the scratch after the call: finish the work first
+    HIP_TRY(hipStreamSynchronize(stream), "knn sync");
+    return GSR_OK;
+}
+
+}  // extern "C"

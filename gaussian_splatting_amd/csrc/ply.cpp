@@ -15,12 +15,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/gsr.h"
 #include "../../include/gsr_ply.h"
-
-namespace gsr {
-int set_error(int code, const char* fmt, ...);  // api.hip
-}
+#include "host.h"
 
 namespace {
 
@@ -118,7 +114,7 @@ int fail(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
-    return gsr::set_error(GSR_ERR_ARGUMENT, "%s", buf);
+    return gsr::fail(GSR_ERR_ARGUMENT, "%s", buf);
 }
 
 }  // namespace

@@ -18,7 +18,9 @@
 // reference makes five passes with a barrier each) and keeps the last 11 filtered
 // rows in registers, so the vertical filter never touches LDS.  The image is read
 // once per tile (plus the halo) and every output is written once: the kernels are
-// HBM-streaming.
+// HBM-streaming.  The C entry points (include/gsr_ssim.h) are at the end of the file.
+#include "../../include/gsr_ssim.h"
+#include "host.h"
 #include "kernels.h"
 
 namespace gsr {
@@ -202,7 +204,7 @@ __global__ void __launch_bounds__(kSsimThreads) ssim_bwd_kernel(int H, int W, co
     }
 }
 
-hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const float* img1, const float* img2,
+static hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const float* img1, const float* img2,
                            float* map, float* dm_dmu1, float* dm_ds11, float* dm_ds12, hipStream_t stream) {
     if (planes <= 0 || H <= 0 || W <= 0) return hipSuccess;
     const dim3 grid((W + kSsimTile - 1) / kSsimTile, (H + kSsimTile - 1) / kSsimTile, planes);
@@ -215,7 +217,7 @@ hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const f
     return hipGetLastError();
 }
 
-hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const float* img2, const float* dL_dmap,
+static hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const float* img2, const float* dL_dmap,
                            const float* dm_dmu1, const float* dm_ds11, const float* dm_ds12, float* dL_dimg1,
                            hipStream_t stream) {
     if (planes <= 0 || H <= 0 || W <= 0) return hipSuccess;
@@ -226,3 +228,43 @@ hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const fl
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_fused_ssim_forward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,
+                           float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, void* stream) {
+    clear_error();
+    if (B < 0 || CH < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARGUMENT, "fused_ssim: negative size");
+    const long long planes = (long long)B * CH;
+    if (planes == 0 || H == 0 || W == 0) return GSR_OK;
+    if (planes > 65535) return fail(GSR_ERR_ARGUMENT, "fused_ssim: B*CH=%lld exceeds 65535 planes", planes);
+    if (!img1 || !img2 || !ssim_map) return fail(GSR_ERR_ARGUMENT, "fused_ssim: null pointer");
+    const int ndm = (dm_dmu1 != nullptr) + (dm_dsigma1_sq != nullptr) + (dm_dsigma12 != nullptr);
+    if (ndm != 0 && ndm != 3) return fail(GSR_ERR_ARGUMENT, "fused_ssim: pass all three derivative maps or none");
+    HIP_TRY(gsr::launch_ssim_fwd((int)planes, H, W, C1, C2, img1, img2, ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
+                                 (hipStream_t)stream),
+            "fused_ssim forward");
+    return GSR_OK;
+}
+
+int gsr_fused_ssim_backward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,
+                            const float* dL_dmap, const float* dm_dmu1, const float* dm_dsigma1_sq,
+                            const float* dm_dsigma12, float* dL_dimg1, void* stream) {
+    (void)C1;  // the derivative maps already carry C1 and C2 (ssim.cu:315-366 does not use them either)
+    (void)C2;
+    clear_error();
+    if (B < 0 || CH < 0 || H < 0 || W < 0) return fail(GSR_ERR_ARGUMENT, "fused_ssim: negative size");
+    const long long planes = (long long)B * CH;
+    if (planes == 0 || H == 0 || W == 0) return GSR_OK;
+    if (planes > 65535) return fail(GSR_ERR_ARGUMENT, "fused_ssim: B*CH=%lld exceeds 65535 planes", planes);
+    if (!img1 || !img2 || !dL_dmap || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg1)
+        return fail(GSR_ERR_ARGUMENT, "fused_ssim backward: null pointer");
+    HIP_TRY(gsr::launch_ssim_bwd((int)planes, H, W, img1, img2, dL_dmap, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1,
+                                 (hipStream_t)stream),
+            "fused_ssim backward");
+    return GSR_OK;
+}
+
+}  // extern "C"

@@ -242,6 +242,18 @@ def test_library_is_the_build_of_this_tree():
     assert build.input_hash(extra=("-DX=1",)) != want  # flags are part of the identity
 
 
+def test_build_identity_covers_every_native_source():
+    """Every .hip, .cpp and .h file under csrc/ is named in build.SOURCES or build.HEADERS: a file the
+    input hash does not cover would leave a stale library looking fresh."""
+    from gaussian_splatting_amd import build
+
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp", ".h"))}
+    listed = set(build.SOURCES) | set(build.HEADERS)
+    assert on_disk - listed == set(), "not in build.SOURCES / build.HEADERS: %s" % sorted(on_disk - listed)
+    assert listed - on_disk == set(), "listed but missing: %s" % sorted(listed - on_disk)
+    assert {f for f in on_disk if f.endswith(".h")} == set(build.HEADERS)
+
+
 def test_build_identity_ignores_the_compiler_path(monkeypatch):
     """the identity is the sources, flags and target, not the compiler's path -- a library
     built with HIPCC=/custom/hipcc loads in a shell without that variable."""
