@@ -242,7 +242,7 @@ def rasterize_gaussians(*args, no_backward: bool = False) -> Tuple[int, torch.Te
     return int(nr.value), out_color, radii, geom, binning, img, out_invdepth
 
 
-def rasterize_gaussians_backward(*args, out=None):
+def rasterize_gaussians_backward(*args, out=None, camera=False):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:149-248).
 
     Positional arguments: the vendored rasterizer's 24 ``(bg, means3D, radii, colors, opacities, scales,
@@ -255,6 +255,10 @@ def rasterize_gaussians_backward(*args, out=None):
     ``out`` (an extension, not in the reference) may map any of the names ``dL_dmeans3D, dL_ddc, dL_dsh,
     dL_dopacity, dL_dscales, dL_drotations`` to preallocated contiguous float32 tensors of the right shape --
     e.g. views of one flat gradient arena that is then all-reduced without a copy.
+    ``camera=True`` (an extension too) also runs the camera backward (include/gsr.h gsr_camera_backward) and
+    returns the tuple above followed by ``(dL_dviewmatrix [4,4], dL_dprojmatrix [4,4], dL_dcampos [3])``: the
+    gradients of the three camera tensors as the forward reads them, entry ``k`` of a flat gradient belonging to
+    ``tensor.contiguous().view(-1)[k]``.
     """
     if len(args) == 25:
         (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -305,7 +309,9 @@ def rasterize_gaussians_backward(*args, out=None):
     else:
         result = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
     if P == 0:
-        return result
+        return result + tuple(torch.zeros(s, **f32) for s in ((4, 4), (4, 4), (3,))) if camera else result
+    # the camera backward reads dL/dconic, which the backward otherwise does not store
+    dL_dconic = alloc((P, 4), **f32) if camera else None
     if accel and not split:
         dL_ddc.zero_()  # no SH evaluation: the dc gradient is zero, as the accel build's zero-initialised tensor
 
@@ -325,7 +331,8 @@ def rasterize_gaussians_backward(*args, out=None):
            binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
            ins.req(dL_dout_color, "dL_dout_color"),
            ins.req(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
-           dL_dmeans2D.data_ptr(), None, dL_dopacity.data_ptr(), dL_dcolors.data_ptr(),
+           dL_dmeans2D.data_ptr(), dL_dconic.data_ptr() if camera else None, dL_dopacity.data_ptr(),
+           dL_dcolors.data_ptr(),
            dL_dinvdepths.data_ptr() if has_inv else None, dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr())
     sh_grads = ((dL_ddc.data_ptr(), dL_dsh.data_ptr() if M > 0 else None) if split else
                 (dL_dsh.data_ptr() if M > 0 else None,))
@@ -335,7 +342,23 @@ def rasterize_gaussians_backward(*args, out=None):
     with torch.cuda.device(device):
         rc = fn(*head, *sh_args, *mid, *sh_grads, *tail)
     _lib.check(rc, "rasterize_gaussians_backward")
-    return result
+    if not camera:
+        return result
+    # every element of the three is written
+    dL_dview, dL_dproj, dL_dcampos = _empty((4, 4), **f32), _empty((4, 4), **f32), _empty((3,), **f32)
+    cam_scratch = torch.empty(0, dtype=torch.uint8, device=device)
+    rc_s = _Resizer(cam_scratch)
+    (p_colors, p_opac, p_scales, _mod, p_rot, p_cov, p_view, p_proj, p_campos, _tx, _ty, p_radii) = mid[:12]
+    p_dc, p_sh = (None, None) if p_colors else (sh_args if split else (None, sh_args[0]))
+    with torch.cuda.device(device):
+        rc = lib.gsr_camera_backward(
+            P, int(degree), M, W, H, head[-1], p_dc, p_sh, p_colors, p_opac, p_scales, float(scale_modifier), p_rot,
+            p_cov, p_view, p_proj, p_campos, float(tan_fovx), float(tan_fovy), p_radii, geomBuffer.data_ptr(),
+            dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(), dL_dcolors.data_ptr(),
+            dL_dinvdepths.data_ptr() if has_inv else None, int(bool(antialiasing)), rc_s.cb, None,
+            _stream_handle(device), dL_dview.data_ptr(), dL_dproj.data_ptr(), dL_dcampos.data_ptr())
+    _lib.check(rc, "camera_backward")
+    return result + (dL_dview, dL_dproj, dL_dcampos)
 
 
 def debug_forward_state(fwd, P: int) -> dict:

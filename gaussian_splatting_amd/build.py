@@ -20,10 +20,10 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libgsr.so")
-SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "backward.hip", "views.hip", "knn.hip", "ssim.hip",
+SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "backward.hip", "views.hip", "camera.hip", "knn.hip", "ssim.hip",
            "adam.hip", "densify.hip", "ply.cpp"]
 # every header under csrc/ (tests/test_host.py checks that no file there is missing from the two lists)
-HEADERS = ["gsr_common.h", "kernels.h", "footprint.h", "host.h", "gauss_bwd_math.h"]
+HEADERS = ["gsr_common.h", "kernels.h", "footprint.h", "host.h", "gauss_bwd_math.h", "camera.h", "camera_math.h"]
 ARCH = os.environ.get("GSR_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result",
@@ -52,10 +52,13 @@ ABI_HEADERS = ("gsr.h", "gsr_knn.h", "gsr_ssim.h", "gsr_adam.h", "gsr_densify.h"
 # views.hip takes exactly backward.hip's flags: its multi-view kernels run the same view_backward
 # (gauss_bwd_math.h), and the view exchange's gradients are bitwise equal to the single-view backward's
 # (tests/test_view_exchange.py) only while both files round that math the same way.
+# camera.hip (the camera backward) restates that math from the backward's own outputs and shares its SH
+# polynomial: the same flags, so its terms round as the dL/dmeans3D terms they mirror.
 _BACKWARD_FLAGS = ["-fno-slp-vectorize", "-ffp-contract=on"]
 FILE_FLAGS = {"render.hip": ["-fno-slp-vectorize"],
               "backward.hip": _BACKWARD_FLAGS,
               "views.hip": _BACKWARD_FLAGS,
+              "camera.hip": _BACKWARD_FLAGS,
               "preprocess.hip": ["-fno-slp-vectorize", "-ffp-contract=off"]}
 
 

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "camera.h"
 #include "host.h"
 #include "kernels.h"
 
@@ -109,6 +110,18 @@ gsr::GeomState carve_geom(char* base, int P, uint32_t gx, uint32_t gy, size_t* t
     *total = align_up(c.off);
     return g;
 }
+
+}  // namespace
+
+namespace gsr {
+// camera.h: the camera backward (camera.hip) reads the forward's SH clamp flags
+const uint8_t* geom_clamped(const void* geom_buffer, int P, int width, int height) {
+    size_t tmp = 0;
+    return carve_geom((char*)geom_buffer, P, (width + kTile - 1) / kTile, (height + kTile - 1) / kTile, &tmp).clamped;
+}
+}  // namespace gsr
+
+namespace {
 
 gsr::ImageState carve_image(char* base, int W, int H, uint32_t tiles, size_t* total) {
     using namespace gsr;

@@ -14,7 +14,7 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "cpu_deep_copy_tuple"]
+           "_RasterizeGaussiansCamera", "cpu_deep_copy_tuple"]
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -45,6 +45,13 @@ def rasterize_gaussians(*args):
     raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
+    # Camera-pose gradients: when a camera tensor of the settings requires grad (and grad mode is on) the three
+    # enter the autograd node as explicit inputs after the settings; every other render takes the path below.
+    s = args[-1]
+    cam = (s.viewmatrix, s.projmatrix, s.campos)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
+        _RasterizeGaussians._no_backward.value = False  # (the camera tensors alone make a backward possible)
+        return _RasterizeGaussiansCamera.apply(*args, *cam)
     # (a render no backward can follow -- grad disabled, or no input requires grad -- skips the atomic backward's
     # accumulator zeroing; autograd's needs_input_grad cannot tell, it ignores the grad mode)
     _RasterizeGaussians._no_backward.value = not (torch.is_grad_enabled() and any(
@@ -113,6 +120,51 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (grad_means3D, grad_means2D, fit(grad_dc, dc), fit(grad_sh, sh),
                 fit(grad_colors_precomp, colors_precomp), grad_opacities, fit(grad_scales, scales),
                 fit(grad_rotations, rotations), fit(grad_cov3Ds_precomp, cov3Ds_precomp), None)
+
+
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """``_RasterizeGaussians`` with the settings' ``viewmatrix``, ``projmatrix`` and ``campos`` as three further
+    inputs after ``raster_settings`` (the same tensors: the forward reads them from the settings), so that
+    ``loss.backward()`` reaches them and whatever they were built from.  The forward is ``_RasterizeGaussians``'s;
+    the backward also runs the camera backward (``_C.rasterize_gaussians_backward(..., camera=True)``).  No
+    reference counterpart; conventions in include/gsr.h ``gsr_camera_backward``."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _RasterizeGaussians.forward(ctx, *args[:-3])
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
+        s = ctx.raster_settings
+        saved = ctx.saved_tensors
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning,
+         img) = saved[:11]
+        dc = saved[11] if ctx.separate_sh else None
+        cam_in = (s.viewmatrix, s.projmatrix, s.campos)
+        view, proj, campos = (t.detach() for t in cam_in)
+        head = (s.bg, means3D, radii, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                view, proj, s.tanfovx, s.tanfovy, grad_out_color, grad_out_depth)
+        tail = (s.sh_degree, campos, geom, ctx.num_rendered, binning, img, s.antialiasing, s.debug)
+        sh_args = (sh,) if dc is None else (dc, sh)
+        *grads, g_view, g_proj, g_campos = _C.rasterize_gaussians_backward(*head, *sh_args, *tail, camera=True)
+
+        def fit(g, like):  # inputs given as empty tensors get no gradient
+            return None if like is None or like.numel() == 0 else g
+
+        n = len(sh_args) + 8  # the inputs before the three camera tensors, the settings among them
+        cam_grads = tuple(g.reshape(t.shape).to(t.device) if ctx.needs_input_grad[n + i] else None
+                          for i, (g, t) in enumerate(zip((g_view, g_proj, g_campos), cam_in)))
+        if dc is None:
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+             grad_scales, grad_rotations) = grads
+            return (grad_means3D, grad_means2D, fit(grad_sh, sh), fit(grad_colors_precomp, colors_precomp),
+                    grad_opacities, fit(grad_scales, scales), fit(grad_rotations, rotations),
+                    fit(grad_cov3Ds_precomp, cov3Ds_precomp), None) + cam_grads
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_dc, grad_sh,
+         grad_scales, grad_rotations) = grads
+        return (grad_means3D, grad_means2D, fit(grad_dc, dc), fit(grad_sh, sh),
+                fit(grad_colors_precomp, colors_precomp), grad_opacities, fit(grad_scales, scales),
+                fit(grad_rotations, rotations), fit(grad_cov3Ds_precomp, cov3Ds_precomp), None) + cam_grads
 
 
 class GaussianRasterizer(nn.Module):

@@ -261,6 +261,34 @@ int gsr_gauss_backward_views_live(int P, int D, int M, const float* means3D, con
                                   float* dL_ddc, float* dL_dsh, float* dL_dopacity, float* dL_dscale, float* dL_drot,
                                   void* stream);
 
+/* Camera-pose gradients (no reference counterpart: the reference's rasterizer treats the camera as a
+ * constant).  Run after gsr_rasterize_backward_ex / _dc of the same forward, on the same stream, with that
+ * call's inputs and five of its per-Gaussian outputs: dL_dmean2D [P,3], dL_dconic [P,4] (which that call must
+ * then be given; 16-byte aligned), dL_dopacity [P], dL_dcolor [P,3] and dL_dinvdepth [P] (NULL if the backward
+ * had none).  Rows of Gaussians with radii == 0 are not read.  geom_buffer is the forward's geometry buffer
+ * (its SH clamp flags are read); width / height are the forward's.  Colours as in the forward: dc + shs (M
+ * rest coefficients), shs alone (dc NULL), or colors_precomp (then dc, shs, D, M and campos are ignored).
+ * Writes every element of
+ *   dL_dviewmatrix [16]  entry k belongs to viewmatrix[k] as the forward reads it; entries 3, 7, 11, 15 (the
+ *                        last column, never read) are zero;
+ *   dL_dprojmatrix [16]  likewise; entries 2, 6, 10, 14 (the depth column, never read) are zero;
+ *   dL_dcampos     [3]   zero with precomputed colours;
+ * and P == 0 gives zeros.  The three tensors are independent inputs, as the forward reads them: viewmatrix
+ * feeds the view-space point (cov2D's Jacobian, the inverse depth) and cov2D's rotation, projmatrix the screen
+ * position, campos the SH view direction.  Conventions are dL_dmean3D's: no gradient through culling, the
+ * radius, the tile rectangle, skips or termination; a clamped view-space x / y is a constant in the Jacobian;
+ * with antialiasing the reference's formula for dL/dcov2D, not the derivative of its forward.
+ * No atomics: for the same per-Gaussian inputs the outputs are the same bit for bit.  scratch_alloc provides
+ * 128 bytes per 1024 Gaussians. */
+int gsr_camera_backward(int P, int D, int M, int width, int height, const float* means3D, const float* dc,
+                        const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                        float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                        const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                        float tan_fovy, const int* radii, const void* geom_buffer, const float* dL_dmean2D,
+                        const float* dL_dconic, const float* dL_dopacity, const float* dL_dcolor,
+                        const float* dL_dinvdepth, int antialiasing, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
+                        void* stream, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos);
+
 /* Frustum test, view-space z > 0.2 (CudaRasterizer::Rasterizer::markVisible).
  * `present` is P bytes (bool). */
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
