@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
-from typing import Optional, Tuple
+from typing import Optional
 
 import torch
 
@@ -25,7 +25,7 @@ __all__ = ["rasterize_gaussians", "rasterize_gaussians_backward", "rasterize_gau
            "gauss_backward_views", "view_block_floats", "view_pack_floats", "view_block_pack", "view_block_unpack", "view_block_index",
            "views_live_floats", "views_live_list",
            "mark_visible", "adamUpdate", "fusedssim",
-           "fusedssim_backward", "forward_rebuilds", "debug_forward_state"]
+           "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha"]
 
 
 # Sync-free forward (gsr_rasterize_forward_ex): the binning buffer is sized from a capacity
@@ -163,8 +163,22 @@ def _own_geometry(geomBuffer: torch.Tensor) -> None:
         _lib.load().gsr_geom_forget(geomBuffer.data_ptr())
 
 
-def rasterize_gaussians(*args, no_backward: bool = False) -> Tuple[int, torch.Tensor, torch.Tensor, torch.Tensor,
-                                                                     torch.Tensor, torch.Tensor, torch.Tensor]:
+def render_alpha(imgBuffer: torch.Tensor, image_height: int, image_width: int) -> torch.Tensor:
+    """The accumulated alpha ``1 - final_T`` [1,H,W] of the forward that filled ``imgBuffer`` (include/gsr.h
+    gsr_render_alpha), on the current stream; zeros for the empty buffer of a forward of no Gaussians."""
+    H, W = int(image_height), int(image_width)
+    device = imgBuffer.device
+    if imgBuffer.numel() == 0:
+        return torch.zeros((1, H, W), dtype=torch.float32, device=device)
+    _require_device(imgBuffer, "imgBuffer")
+    alpha = _empty((1, H, W), dtype=torch.float32, device=device)  # every pixel is written
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_alpha(W, H, imgBuffer.data_ptr(), alpha.data_ptr(), _stream_handle(device))
+    _lib.check(rc, "render_alpha")
+    return alpha
+
+
+def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = False) -> tuple:
     """RasterizeGaussiansCUDA (rasterize_points.cu:45-146).
 
     Positional arguments, as the pybind function takes them:
@@ -178,6 +192,10 @@ def rasterize_gaussians(*args, no_backward: bool = False) -> Tuple[int, torch.Te
     ``no_backward`` (an extension): no backward will follow (an eval / no_grad render), so the forward does not
     zero the atomic backward's accumulator rows beside its render ("bwd_atomic" 0 for this call; a backward
     of it would take the record path).
+
+    ``return_alpha`` (an extension): the accumulated alpha ``1 - final_T`` [1,H,W] is appended to the returned
+    tuple (one more small kernel, include/gsr.h gsr_render_alpha; zeros when there are no Gaussians).  Without
+    it nothing more is launched or allocated.
     """
     if len(args) == 21:
         (background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -206,7 +224,8 @@ def rasterize_gaussians(*args, no_backward: bool = False) -> Tuple[int, torch.Te
     binning = torch.empty(0, dtype=torch.uint8, device=device)
     img = torch.empty(0, dtype=torch.uint8, device=device)
     if P == 0:
-        return 0, out_color, radii, geom, binning, img, out_invdepth
+        fwd = (0, out_color, radii, geom, binning, img, out_invdepth)
+        return fwd + (torch.zeros((1, H, W), **f32),) if return_alpha else fwd
 
     M = sh.size(1) if _present(sh) else 0
     split = dc is not None and _present(dc) and not _present(colors)
@@ -239,10 +258,11 @@ def rasterize_gaussians(*args, no_backward: bool = False) -> Tuple[int, torch.Te
     _note_rendered(key, P, nr.value)
     # The binning buffer's layout (its capacity) is recovered by the backward from the buffer's
     # size (include/gsr.h gsr_rasterize_backward_ex), so nothing rides on the tensor object.
-    return int(nr.value), out_color, radii, geom, binning, img, out_invdepth
+    fwd = (int(nr.value), out_color, radii, geom, binning, img, out_invdepth)
+    return fwd + (render_alpha(img, H, W),) if return_alpha else fwd
 
 
-def rasterize_gaussians_backward(*args, out=None, camera=False):
+def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=None):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:149-248).
 
     Positional arguments: the vendored rasterizer's 24 ``(bg, means3D, radii, colors, opacities, scales,
@@ -259,6 +279,10 @@ def rasterize_gaussians_backward(*args, out=None, camera=False):
     returns the tuple above followed by ``(dL_dviewmatrix [4,4], dL_dprojmatrix [4,4], dL_dcampos [3])``: the
     gradients of the three camera tensors as the forward reads them, entry ``k`` of a flat gradient belonging to
     ``tensor.contiguous().view(-1)[k]``.
+    ``dL_dout_alpha`` (an extension): the gradient [1,H,W] of the accumulated-alpha output
+    (``rasterize_gaussians(..., return_alpha=True)``); its share is added to every returned gradient it reaches
+    (include/gsr.h gsr_rasterize_backward_alpha) and, with ``camera=True``, to the camera gradients.  None or
+    an empty tensor: no alpha loss, the call and its results are those without the keyword.
     """
     if len(args) == 25:
         (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -338,9 +362,21 @@ def rasterize_gaussians_backward(*args, out=None, camera=False):
                 (dL_dsh.data_ptr() if M > 0 else None,))
     tail = (dL_dscales.data_ptr(), dL_drotations.data_ptr(), int(bool(antialiasing)), int(bool(debug)), rs.cb, None,
             _stream_handle(device), 0, int(binningBuffer.numel()))
-    fn = lib.gsr_rasterize_backward_dc if split else lib.gsr_rasterize_backward_ex
-    with torch.cuda.device(device):
-        rc = fn(*head, *sh_args, *mid, *sh_grads, *tail)
+    if dL_dout_alpha is not None and dL_dout_alpha.numel() != 0:
+        if dL_dout_alpha.numel() != H * W:
+            raise RuntimeError(f"dL_dout_alpha: expected {(1, H, W)} values, got {tuple(dL_dout_alpha.shape)}")
+        # gsr_rasterize_backward_alpha: the _dc argument list (dc NULL = combined shs) with dL_dalphas after
+        # dL_dinvdepths
+        n_in = 17  # mid: the inputs and upstream gradients up to dL_dinvdepths
+        sh_in = sh_args if split else (None,) + sh_args
+        sh_out = sh_grads if split else (None,) + sh_grads
+        with torch.cuda.device(device):
+            rc = lib.gsr_rasterize_backward_alpha(*head, *sh_in, *mid[:n_in], ins.req(dL_dout_alpha, "dL_dout_alpha"),
+                                                  *mid[n_in:], *sh_out, *tail)
+    else:
+        fn = lib.gsr_rasterize_backward_dc if split else lib.gsr_rasterize_backward_ex
+        with torch.cuda.device(device):
+            rc = fn(*head, *sh_args, *mid, *sh_grads, *tail)
     _lib.check(rc, "rasterize_gaussians_backward")
     if not camera:
         return result

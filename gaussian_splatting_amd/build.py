@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libgsr.so")
-SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "backward.hip", "views.hip", "camera.hip", "knn.hip", "ssim.hip",
+SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "alpha.hip", "backward.hip", "views.hip", "camera.hip", "knn.hip", "ssim.hip",
            "adam.hip", "densify.hip", "ply.cpp"]
 # every header under csrc/ (tests/test_host.py checks that no file there is missing from the two lists)
 HEADERS = ["gsr_common.h", "kernels.h", "footprint.h", "host.h", "gauss_bwd_math.h", "camera.h", "camera_math.h"]

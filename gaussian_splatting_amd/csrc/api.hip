@@ -950,7 +950,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
                   float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc,
                   float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
                   void* scratch_ctx, void* stream_, int binning_capacity, size_t binning_bytes,
-                  float* view_block = nullptr) {
+                  const float* dL_dalphas = nullptr, float* view_block = nullptr) {
     using namespace gsr;
     HostTimer host_time(g_bwd_host);
     clear_error();
@@ -1102,6 +1102,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
         ra.W = width; ra.H = height; ra.gx = gx; ra.gy = gy; ra.ranges = img.ranges; ra.gid_sorted = bin.gid_sorted;
         ra.rec = geom.rec;
         ra.bg = background; ra.dL_dpix = dL_dpix; ra.dL_dinvdepth = dL_dinvdepths; ra.img = img; ra.recs = recs;
+        ra.dL_dalpha = dL_dalphas;
         ra.ckpt = bin.ckpt; ra.seg_ck = geom.fwd_seg_ck; ra.rec_start = geom.rec_start;
         ra.unit_cnt = geom.unit_cnt; ra.unit_part = geom.unit_part; ra.unit_full = bin.unit_full;
         ra.full_cap = (uint32_t)unit_full_cap(C);
@@ -1251,6 +1252,40 @@ int gsr_rasterize_backward_dc(int P, int D, int M, int R, const float* backgroun
                          binning_capacity, binning_bytes);
 }
 
+int gsr_render_alpha(int width, int height, const void* image_buffer, float* out_alpha, void* stream) {
+    using namespace gsr;
+    clear_error();
+    if (width <= 0 || height <= 0)
+        return fail(GSR_ERR_ARGUMENT, "render_alpha: invalid sizes W=%d H=%d", width, height);
+    if (!image_buffer || !out_alpha) return fail(GSR_ERR_ARGUMENT, "render_alpha: null pointer");
+    const uint32_t gx = (width + kTile - 1) / kTile, gy = (height + kTile - 1) / kTile;
+    size_t tmp = 0;
+    const ImageState img = carve_image((char*)const_cast<void*>(image_buffer), width, height, gx * gy, &tmp);
+    HIP_TRY(launch_render_alpha(img.final_T, out_alpha, width, height, (hipStream_t)stream), "render_alpha");
+    return GSR_OK;
+}
+
+int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
+                                 const float* means3D, const float* dc, const float* shs,
+                                 const float* colors_precomp, const float* opacities, const float* scales,
+                                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                 const float* viewmatrix, const float* projmatrix, const float* campos,
+                                 float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
+                                 void* binning_buffer, void* image_buffer, const float* dL_dpix,
+                                 const float* dL_dinvdepths, const float* dL_dalphas, float* dL_dmean2D,
+                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth,
+                                 float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
+                                 float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
+                                 void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes) {
+    // (dc == NULL: the combined layout, shs holding every coefficient; dL_ddc is then not written)
+    return backward_impl(P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
+                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
+                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, dc ? dL_ddc : nullptr,
+                         dL_dsh, dL_dscale, dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream,
+                         binning_capacity, binning_bytes, dL_dalphas);
+}
+
 }  // extern "C"
 
 int gsr_rasterize_backward_screen(int P, int D, int M, int R, const float* background, int width, int height,
@@ -1269,7 +1304,7 @@ int gsr_rasterize_backward_screen(int P, int D, int M, int R, const float* backg
                          scale_modifier, rotations, nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
                          geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, nullptr, nullptr, nullptr,
                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, antialiasing, debug,
-                         scratch_alloc, scratch_ctx, stream, binning_capacity, binning_bytes, view_block);
+                         scratch_alloc, scratch_ctx, stream, binning_capacity, binning_bytes, nullptr, view_block);
 }
 
 int gsr_debug_forward_state(int P, int width, int height, int R, int binning_capacity, size_t binning_bytes,

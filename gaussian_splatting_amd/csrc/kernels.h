@@ -110,6 +110,10 @@ struct RenderBwdArgs {
     // or null for the per-instance gradient records + gauss_reduce
     float* acc;
     uint32_t* touched;
+    // upstream gradient of the accumulated-alpha output (alpha.hip), [H,W], or null: folded into the
+    // seed of the per-pixel scalar gB beside the background term, whose form it shares (non-null selects
+    // render_bwd's ALPHA instantiations; the others never read it)
+    const float* dL_dalpha;
 };
 
 struct GaussBwdArgs {
@@ -430,6 +434,8 @@ hipError_t launch_render_fwd(const RenderFwdArgs& a, hipStream_t stream, int qua
 hipError_t launch_render_fwd_redo(const RenderFwdArgs& a, hipStream_t stream, int quads = 2);
 // a tile-major pixel plane (tile_px) -> image order [H][W], 4-byte elements (inspection only)
 hipError_t launch_untile(const uint32_t* src, uint32_t* dst, int W, int H, uint32_t gx, hipStream_t stream);
+// alpha.hip: the tile-major final_T plane (ImageState) -> accumulated alpha 1 - final_T, row-major [H][W]
+hipError_t launch_render_alpha(const float* final_T, float* out_alpha, int W, int H, hipStream_t stream);
 // grid_mode ("bwd_grid" option): 0 = strided when the worst-case grid is far larger than the tiles,
 // 1 = one block per possible unit, 2 = strided
 hipError_t launch_render_bwd(const RenderBwdArgs& a, size_t max_units, hipStream_t stream, int grid_mode = 0);

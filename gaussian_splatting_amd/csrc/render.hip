@@ -511,7 +511,13 @@ hipError_t launch_render_fwd(const RenderFwdArgs& a, hipStream_t stream, int qua
 // run ~17x slower).  The summation order over a Gaussian's instances then follows the hardware, so
 // the result is not bitwise reproducible; the record path (bwd_atomic=0) is.  The default since r5f:
 // 1M@1080p 0.7335 -> 0.7320 ms, 5M@4K 2.328 -> 2.224 ms (gauss_reduce gone; profiles/r05/r5f).
-template <bool CENSUS, bool STRIDED, bool ATOMIC>
+// ALPHA: an upstream gradient of the accumulated-alpha output (RenderBwdArgs::dL_dalpha non-null) is loaded in
+// the prologue and folded into the seed of gB; the launcher picks the instantiation by the pointer.  A compile-
+// time flag, not a test of the pointer in the kernel: the compiler turns each nullable load of the prologue into
+// a scalar branch around it, and four more of those in every unit cost a backward with no alpha gradient
+// +0.28% of the 1M@1080p step (0.6919 -> 0.6938 ms over ten interleaved pairs).  With
+// ALPHA false the kernel is the one without the feature.
+template <bool CENSUS, bool STRIDED, bool ATOMIC, bool ALPHA>
 __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
   {
     // One wave per unit = (tile, segment): the entries [start, end) of the tile's list, start a
@@ -574,7 +580,7 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
     int nc[4];
     // Every slot's pixel state is loaded with no branch in between (an outside pixel reads a
     // clamped, valid address and is zeroed afterwards), so all the loads are in flight at once.
-    float c0[4], c1[4], c2[4], cd[4], fT[4], k0[4], k1[4], k2[4], k3[4], k4[4];
+    float c0[4], c1[4], c2[4], cd[4], fT[4], k0[4], k1[4], k2[4], k3[4], k4[4], ga[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const int px = min(tile_x0 + (q & 1) * 8 + lx, a.W - 1), py = min(tile_y0 + (q >> 1) * 8 + ly, a.H - 1);
@@ -584,6 +590,7 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
         g1[q] = a.dL_dpix[N + pix];
         g2[q] = a.dL_dpix[2 * N + pix];
         gi[q] = a.dL_dinvdepth ? a.dL_dinvdepth[pix] : 0.f;
+        ga[q] = ALPHA ? a.dL_dalpha[pix] : 0.f;  // (the accumulated-alpha output's gradient; only the seed below reads it)
         c0[q] = a.img.accum[t];
         c1[q] = a.img.accum[NT + t];
         c2[q] = a.img.accum[2 * NT + t];
@@ -609,9 +616,13 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
         gi[q] = in ? gi[q] : 0.f;
         T[q] = k0[q];
         // dL/dpix . (what the forward accumulated from `start` on) + the background term of
-        // dL/dalpha (CR/backward.cu:587-590); shrinks to "behind this entry" as the walk proceeds
+        // dL/dalpha (CR/backward.cu:587-590); shrinks to "behind this entry" as the walk proceeds.
+        // The accumulated-alpha output A = 1 - final_T has dA/dalpha_i = +final_T / (1 - alpha_i), the
+        // background term's form with -1 for bg . dL/dpix: its gradient ga enters here and nowhere else
+        // (without one ga is the constant 0 and x - 0 is x: the expression without the term).
         gB[q] = in ? g0[q] * (c0[q] - k1[q]) + g1[q] * (c1[q] - k2[q]) + g2[q] * (c2[q] - k3[q]) +
-                         gi[q] * (cd[q] - k4[q]) + fT[q] * (a.bg[0] * g0[q] + a.bg[1] * g1[q] + a.bg[2] * g2[q])
+                         gi[q] * (cd[q] - k4[q]) +
+                         fT[q] * (a.bg[0] * g0[q] + a.bg[1] * g1[q] + a.bg[2] * g2[q] - ga[q])
                    : 0.f;
     }
     // Per-slot limits: entries at positions >= slim[q] reach no pixel of slot q (the forward
@@ -816,14 +827,14 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
 // own seg_ck is on the device only; surplus blocks exit at the unit lookup)
 size_t bwd_max_units(size_t R, uint32_t tiles, int seg_ck) { return R / ((size_t)seg_ck * kCkStride) + tiles; }
 
-template <bool ATOMIC>
+template <bool ATOMIC, bool ALPHA>
 static void launch_render_bwd_t(const RenderBwdArgs& a, uint32_t grid, bool strided, hipStream_t stream) {
     if (a.census)
-        hipLaunchKernelGGL((render_bwd_kernel<true, false, ATOMIC>), dim3(grid), dim3(kWave), 0, stream, a);
+        hipLaunchKernelGGL((render_bwd_kernel<true, false, ATOMIC, ALPHA>), dim3(grid), dim3(kWave), 0, stream, a);
     else if (strided)
-        hipLaunchKernelGGL((render_bwd_kernel<false, true, ATOMIC>), dim3(grid), dim3(kWave), 0, stream, a);
+        hipLaunchKernelGGL((render_bwd_kernel<false, true, ATOMIC, ALPHA>), dim3(grid), dim3(kWave), 0, stream, a);
     else
-        hipLaunchKernelGGL((render_bwd_kernel<false, false, ATOMIC>), dim3(grid), dim3(kWave), 0, stream, a);
+        hipLaunchKernelGGL((render_bwd_kernel<false, false, ATOMIC, ALPHA>), dim3(grid), dim3(kWave), 0, stream, a);
 }
 
 // The strided grid: kBwdGridTiles unit blocks per tile, used when the worst-case grid (max_units) is
@@ -834,10 +845,14 @@ hipError_t launch_render_bwd(const RenderBwdArgs& a, size_t max_units, hipStream
     const size_t strided_units = std::min(max_units, (size_t)kBwdGridTiles * a.gx * a.gy);
     const bool strided = !a.census && (grid_mode == 2 || (grid_mode == 0 && max_units > kBwdStrideRatio * strided_units));
     const uint32_t grid = (uint32_t)(strided ? strided_units : max_units) + a.fill_blocks;  // fill blocks first
-    if (a.acc)
-        launch_render_bwd_t<true>(a, grid, strided, stream);
+    if (a.acc && a.dL_dalpha)
+        launch_render_bwd_t<true, true>(a, grid, strided, stream);
+    else if (a.acc)
+        launch_render_bwd_t<true, false>(a, grid, strided, stream);
+    else if (a.dL_dalpha)
+        launch_render_bwd_t<false, true>(a, grid, strided, stream);
     else
-        launch_render_bwd_t<false>(a, grid, strided, stream);
+        launch_render_bwd_t<false, false>(a, grid, strided, stream);
     return hipGetLastError();
 }
 

@@ -40,11 +40,15 @@ class GaussianRasterizationSettings(NamedTuple):
     antialiasing: bool
 
 
-def rasterize_gaussians(*args):
+def rasterize_gaussians(*args, return_alpha=False):
     """``rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-    raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``."""
+    raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``.
+
+    ``return_alpha=True`` (an extension): returns ``(color, radii, invdepths, alpha)``, ``alpha`` [1,H,W] the
+    accumulated opacity ``1 - final_T`` of every pixel, differentiable like the other two maps."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
+    _RasterizeGaussians._return_alpha.value = bool(return_alpha)  # (read and cleared by the node's forward)
     # Camera-pose gradients: when a camera tensor of the settings requires grad (and grad mode is on) the three
     # enter the autograd node as explicit inputs after the settings; every other render takes the path below.
     s = args[-1]
@@ -71,6 +75,23 @@ class _RasterizeGaussians(torch.autograd.Function):
     """
 
     _no_backward = threading.local()
+    _return_alpha = threading.local()  # set by rasterize_gaussians(..., return_alpha=True) for its one call
+
+    @staticmethod
+    def _upstream(ctx, grad_out_color, grad_out_depth, grad_alpha):
+        """The upstream gradients as _C.rasterize_gaussians_backward takes them: ``(color, depth, keywords)``.
+        A node with an alpha output does not materialise missing gradients, so an unused alpha map costs
+        nothing (None -> NULL); colour and depth are then filled in as autograd would have."""
+        if not ctx.with_alpha:
+            return grad_out_color, grad_out_depth, {}
+        s = ctx.raster_settings
+        f32 = dict(dtype=torch.float32, device=ctx.saved_tensors[1].device)
+        if grad_out_color is None:
+            grad_out_color = torch.zeros((3, s.image_height, s.image_width), **f32)
+        if grad_out_depth is None:
+            grad_out_depth = torch.zeros((1, s.image_height, s.image_width), **f32)
+        return grad_out_color, grad_out_depth, ({} if not grad_alpha or grad_alpha[0] is None else
+                                                {"dL_dout_alpha": grad_alpha[0]})
 
     @staticmethod
     def forward(ctx, *args):
@@ -85,20 +106,30 @@ class _RasterizeGaussians(torch.autograd.Function):
         sh_args = (sh,) if dc is None else (dc, sh)
         no_backward = getattr(_RasterizeGaussians._no_backward, "value", False)
         _RasterizeGaussians._no_backward.value = False  # (set by rasterize_gaussians for this call only)
-        num_rendered, color, radii, geom, binning, img, invdepths = _C.rasterize_gaussians(
-            *head, *sh_args, *tail, no_backward=no_backward)
+        with_alpha = getattr(_RasterizeGaussians._return_alpha, "value", False)
+        _RasterizeGaussians._return_alpha.value = False
+        ctx.with_alpha = with_alpha
+        if with_alpha:
+            num_rendered, color, radii, geom, binning, img, invdepths, alpha = _C.rasterize_gaussians(
+                *head, *sh_args, *tail, no_backward=no_backward, return_alpha=True)
+            ctx.set_materialize_grads(False)
+        else:
+            num_rendered, color, radii, geom, binning, img, invdepths = _C.rasterize_gaussians(
+                *head, *sh_args, *tail, no_backward=no_backward)
         ctx.raster_settings = s
         ctx.num_rendered = num_rendered
         ctx.separate_sh = dc is not None
         saved = (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning, img)
         ctx.save_for_backward(*saved, *(() if dc is None else (dc,)))
         ctx.mark_non_differentiable(radii)
-        return color, radii, invdepths
+        return (color, radii, invdepths, alpha) if with_alpha else (color, radii, invdepths)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *grad_alpha):
         s = ctx.raster_settings
         saved = ctx.saved_tensors
+        grad_out_color, grad_out_depth, alpha_kw = _RasterizeGaussians._upstream(ctx, grad_out_color, grad_out_depth,
+                                                                                 grad_alpha)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning,
          img) = saved[:11]
         dc = saved[11] if ctx.separate_sh else None
@@ -111,12 +142,12 @@ class _RasterizeGaussians(torch.autograd.Function):
 
         if dc is None:
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*head, sh, *tail)
+             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*head, sh, *tail, **alpha_kw)
             return (grad_means3D, grad_means2D, fit(grad_sh, sh), fit(grad_colors_precomp, colors_precomp),
                     grad_opacities, fit(grad_scales, scales), fit(grad_rotations, rotations),
                     fit(grad_cov3Ds_precomp, cov3Ds_precomp), None)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_dc, grad_sh,
-         grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*head, dc, sh, *tail)
+         grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*head, dc, sh, *tail, **alpha_kw)
         return (grad_means3D, grad_means2D, fit(grad_dc, dc), fit(grad_sh, sh),
                 fit(grad_colors_precomp, colors_precomp), grad_opacities, fit(grad_scales, scales),
                 fit(grad_rotations, rotations), fit(grad_cov3Ds_precomp, cov3Ds_precomp), None)
@@ -134,9 +165,11 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
         return _RasterizeGaussians.forward(ctx, *args[:-3])
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *grad_alpha):
         s = ctx.raster_settings
         saved = ctx.saved_tensors
+        grad_out_color, grad_out_depth, alpha_kw = _RasterizeGaussians._upstream(ctx, grad_out_color, grad_out_depth,
+                                                                                 grad_alpha)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning,
          img) = saved[:11]
         dc = saved[11] if ctx.separate_sh else None
@@ -146,7 +179,8 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 view, proj, s.tanfovx, s.tanfovy, grad_out_color, grad_out_depth)
         tail = (s.sh_degree, campos, geom, ctx.num_rendered, binning, img, s.antialiasing, s.debug)
         sh_args = (sh,) if dc is None else (dc, sh)
-        *grads, g_view, g_proj, g_campos = _C.rasterize_gaussians_backward(*head, *sh_args, *tail, camera=True)
+        *grads, g_view, g_proj, g_campos = _C.rasterize_gaussians_backward(*head, *sh_args, *tail, camera=True,
+                                                                            **alpha_kw)
 
         def fit(g, like):  # inputs given as empty tensors get no gradient
             return None if like is None or like.numel() == 0 else g
@@ -180,10 +214,11 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None):
+                cov3D_precomp=None, dc=None, return_alpha=False):
         """Same checks as the reference (:242-261).  ``dc=`` (keyword) selects the 3DGS-accel separate-SH
         input: ``dc`` = ``_features_dc`` [P,1,3] and ``shs`` = ``_features_rest`` [P,M,3]
-        (gaussian_renderer/__init__.py:115-125)."""
+        (gaussian_renderer/__init__.py:115-125).  ``return_alpha=True`` returns ``(color, radii, invdepths,
+        alpha)`` with the differentiable accumulated-alpha map [1,H,W] (``rasterize_gaussians``)."""
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -198,7 +233,7 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         if dc is None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, s)
+                                       cov3D_precomp, s, return_alpha=return_alpha)
         dc = empty if colors_precomp.numel() != 0 else dc
         return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, s)
+                                   cov3D_precomp, s, return_alpha=return_alpha)

@@ -160,6 +160,42 @@ int gsr_rasterize_backward_dc(int P, int D, int M, int R, const float* backgroun
                               int antialiasing, int debug, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
                               void* stream, int binning_capacity, size_t binning_bytes);
 
+/* Accumulated alpha (silhouette): a third differentiable map beside colour and inverse depth,
+ * A[pix] = 1 - final_T[pix], final_T the transmittance after the pixel's last contributor -- the
+ * factor of the background in out_color (CR/forward.cu:497-505).  A pixel no Gaussian reaches has
+ * A == 0.0 exactly.  No reference counterpart; the forward keeps final_T in its image buffer anyway.
+ *
+ * gsr_render_alpha: writes A ([1,H,W], row-major, every element) from the image buffer of a finished
+ *   forward of the same width and height (any of the three), one small kernel on `stream`; call it after
+ *   the forward, on the forward's stream or one ordered behind it.  Valid only for P > 0 (a forward of no
+ *   Gaussians allocates no image buffer: A is then all zeros).  GSR_ERR_ARGUMENT on non-positive sizes or
+ *   a NULL pointer.
+ * gsr_rasterize_backward_alpha: gsr_rasterize_backward_dc with an upstream gradient dL_dalphas ([1,H,W],
+ *   may be NULL: then exactly gsr_rasterize_backward_dc) of A.  dA/dalpha_i = +final_T / (1 - alpha_i) has
+ *   the form of the colour's background term (CR/backward.cu:587-590) with -1 in place of bg . dL_dpix, and
+ *   enters the blend backward there; the conventions are the colour's (no gradient through the early
+ *   termination, the skip tests or the 0.99 clamp).  Every output carries the alpha loss's share except
+ *   dL_dcolor / dL_dsh / dL_ddc / dL_dinvdepth, which it does not reach.  Unlike _dc, dc may be NULL: shs is
+ *   then the combined [P,M,3] array as in gsr_rasterize_backward_ex and dL_ddc is not written (what
+ *   gsr_rasterize_backward_screen accepts).  gsr_camera_backward, run on the outputs, gives the camera
+ *   gradients of the alpha loss too (campos gets none: A does not depend on the colours).  Not supported
+ *   yet: the multi-GPU view blocks (gsr_rasterize_backward_screen takes no dL_dalphas) and a gradient
+ *   for the background. */
+int gsr_render_alpha(int width, int height, const void* image_buffer, float* out_alpha, void* stream);
+
+int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
+                                 const float* means3D, const float* dc, const float* shs,
+                                 const float* colors_precomp, const float* opacities, const float* scales,
+                                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                 const float* viewmatrix, const float* projmatrix, const float* campos,
+                                 float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
+                                 void* binning_buffer, void* image_buffer, const float* dL_dpix,
+                                 const float* dL_dinvdepths, const float* dL_dalphas, float* dL_dmean2D,
+                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth,
+                                 float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
+                                 float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
+                                 void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes);
+
 /* Multi-GPU view exchange (gaussian_splatting_amd/distributed.py
  * ViewExchange).  The reference trains on one GPU; sharding views over N ranks needs the
  * N views' parameter gradients summed on every rank.  Instead of all-reducing the 59-float
