@@ -262,7 +262,7 @@ def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = F
     return fwd + (render_alpha(img, H, W),) if return_alpha else fwd
 
 
-def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=None):
+def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=None, absgrad=False):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:149-248).
 
     Positional arguments: the vendored rasterizer's 24 ``(bg, means3D, radii, colors, opacities, scales,
@@ -283,6 +283,10 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
     (``rasterize_gaussians(..., return_alpha=True)``); its share is added to every returned gradient it reaches
     (include/gsr.h gsr_rasterize_backward_alpha) and, with ``camera=True``, to the camera gradients.  None or
     an empty tensor: no alpha loss, the call and its results are those without the keyword.
+    ``absgrad=True`` (an extension): the absolute screen-space gradient [P,3] (include/gsr.h
+    gsr_rasterize_backward_abs: per Gaussian the sum over pixels of the absolute value of each pixel's term of
+    ``dL_dmeans2D``, column 2 zero) is appended as the LAST element of the returned tuple, after the camera
+    gradients when ``camera=True``.  Without it the call and its results are those without the keyword.
     """
     if len(args) == 25:
         (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -333,7 +337,9 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
     else:
         result = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
     if P == 0:
-        return result + tuple(torch.zeros(s, **f32) for s in ((4, 4), (4, 4), (3,))) if camera else result
+        result = result + tuple(torch.zeros(s, **f32) for s in ((4, 4), (4, 4), (3,))) if camera else result
+        return result + (torch.zeros((P, 3), **f32),) if absgrad else result
+    dL_dabs = alloc((P, 3), **f32) if absgrad else None  # every element is written
     # the camera backward reads dL/dconic, which the backward otherwise does not store
     dL_dconic = alloc((P, 4), **f32) if camera else None
     if accel and not split:
@@ -362,24 +368,30 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
                 (dL_dsh.data_ptr() if M > 0 else None,))
     tail = (dL_dscales.data_ptr(), dL_drotations.data_ptr(), int(bool(antialiasing)), int(bool(debug)), rs.cb, None,
             _stream_handle(device), 0, int(binningBuffer.numel()))
-    if dL_dout_alpha is not None and dL_dout_alpha.numel() != 0:
-        if dL_dout_alpha.numel() != H * W:
-            raise RuntimeError(f"dL_dout_alpha: expected {(1, H, W)} values, got {tuple(dL_dout_alpha.shape)}")
+    has_alpha = dL_dout_alpha is not None and dL_dout_alpha.numel() != 0
+    if has_alpha and dL_dout_alpha.numel() != H * W:
+        raise RuntimeError(f"dL_dout_alpha: expected {(1, H, W)} values, got {tuple(dL_dout_alpha.shape)}")
+    if has_alpha or absgrad:
         # gsr_rasterize_backward_alpha: the _dc argument list (dc NULL = combined shs) with dL_dalphas after
-        # dL_dinvdepths
+        # dL_dinvdepths; gsr_rasterize_backward_abs: the same with dL_dmean2D_abs at the end
         n_in = 17  # mid: the inputs and upstream gradients up to dL_dinvdepths
         sh_in = sh_args if split else (None,) + sh_args
         sh_out = sh_grads if split else (None,) + sh_grads
+        p_alpha = ins.req(dL_dout_alpha, "dL_dout_alpha") if has_alpha else None
         with torch.cuda.device(device):
-            rc = lib.gsr_rasterize_backward_alpha(*head, *sh_in, *mid[:n_in], ins.req(dL_dout_alpha, "dL_dout_alpha"),
-                                                  *mid[n_in:], *sh_out, *tail)
+            if absgrad:
+                rc = lib.gsr_rasterize_backward_abs(*head, *sh_in, *mid[:n_in], p_alpha, *mid[n_in:], *sh_out, *tail,
+                                                    dL_dabs.data_ptr())
+            else:
+                rc = lib.gsr_rasterize_backward_alpha(*head, *sh_in, *mid[:n_in], p_alpha, *mid[n_in:], *sh_out,
+                                                      *tail)
     else:
         fn = lib.gsr_rasterize_backward_dc if split else lib.gsr_rasterize_backward_ex
         with torch.cuda.device(device):
             rc = fn(*head, *sh_args, *mid, *sh_grads, *tail)
     _lib.check(rc, "rasterize_gaussians_backward")
     if not camera:
-        return result
+        return result + (dL_dabs,) if absgrad else result
     # every element of the three is written
     dL_dview, dL_dproj, dL_dcampos = _empty((4, 4), **f32), _empty((4, 4), **f32), _empty((3,), **f32)
     cam_scratch = torch.empty(0, dtype=torch.uint8, device=device)
@@ -394,7 +406,8 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
             dL_dinvdepths.data_ptr() if has_inv else None, int(bool(antialiasing)), rc_s.cb, None,
             _stream_handle(device), dL_dview.data_ptr(), dL_dproj.data_ptr(), dL_dcampos.data_ptr())
     _lib.check(rc, "camera_backward")
-    return result + (dL_dview, dL_dproj, dL_dcampos)
+    result = result + (dL_dview, dL_dproj, dL_dcampos)
+    return result + (dL_dabs,) if absgrad else result
 
 
 def debug_forward_state(fwd, P: int) -> dict:

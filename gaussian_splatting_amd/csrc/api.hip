@@ -950,7 +950,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
                   float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc,
                   float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
                   void* scratch_ctx, void* stream_, int binning_capacity, size_t binning_bytes,
-                  const float* dL_dalphas = nullptr, float* view_block = nullptr) {
+                  const float* dL_dalphas = nullptr, float* view_block = nullptr, float* dL_dmean2D_abs = nullptr) {
     using namespace gsr;
     HostTimer host_time(g_bwd_host);
     clear_error();
@@ -978,6 +978,10 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
             return fail(GSR_ERR_ARGUMENT, "rasterize_backward: dL_dinvdepths and dL_dinvdepth go together");
     }
     if (dc && M > 0 && !shs) return fail(GSR_ERR_ARGUMENT, "rasterize_backward: %d rest SH coefficients but no shs", M);
+    if (dL_dmean2D_abs && screen)
+        return fail(GSR_ERR_ARGUMENT, "rasterize_backward: the view-block backward has no absolute gradient");
+    if (dL_dmean2D_abs && g_census)  // (render_bwd has no CENSUS x ABSGRAD instantiation)
+        return fail(GSR_ERR_ARGUMENT, "rasterize_backward: dL_dmean2D_abs cannot be combined with the census");
     if (dc) M += 1;  // as in the forward
     if (!colors_precomp && (shs || dc) && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
         return fail(GSR_ERR_ARGUMENT, "rasterize_backward: SH degree %d needs %d coefficients, got %d", D,
@@ -1034,6 +1038,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
     // dense outputs to zero-fill (gauss_bwd then writes only the non-zero rows)
     FillArgs fill{};
     const int m_rest = dc ? M - 1 : M;
+    static_assert(kFillSegs >= 12, "the eleven dense outputs and the absolute gradient");
     auto seg = [&](float* ptr, size_t n) {
         if (ptr && n) {
             fill.ptr[fill.count] = ptr;
@@ -1043,6 +1048,9 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
     };
     if (zmode) {
         seg(dL_dmean2D, 3 * (size_t)P);
+        // (the absolute gradient: beside it on the atomic path, whose gauss_bwd writes the touched rows only;
+        // on the record path gauss_reduce writes every row and no fill may race it)
+        if (atomic) seg(dL_dmean2D_abs, 3 * (size_t)P);
         seg(dL_dconic, 4 * (size_t)P);
         seg(dL_dopacity, (size_t)P);
         seg(dL_dcolor, 3 * (size_t)P);
@@ -1103,6 +1111,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
         ra.rec = geom.rec;
         ra.bg = background; ra.dL_dpix = dL_dpix; ra.dL_dinvdepth = dL_dinvdepths; ra.img = img; ra.recs = recs;
         ra.dL_dalpha = dL_dalphas;
+        ra.absgrad = dL_dmean2D_abs != nullptr;
         ra.ckpt = bin.ckpt; ra.seg_ck = geom.fwd_seg_ck; ra.rec_start = geom.rec_start;
         ra.unit_cnt = geom.unit_cnt; ra.unit_part = geom.unit_part; ra.unit_full = bin.unit_full;
         ra.full_cap = (uint32_t)unit_full_cap(C);
@@ -1127,7 +1136,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
         // (nothing between render_bwd and gauss_bwd: gauss_bwd lists the touched Gaussians itself)
     } else {
         StageScope sc(ST_GAUSS_REDUCE, stream);
-        HIP_TRY(launch_gauss_reduce(P, geom, recs, sums, flags, radii, live, live_count, stream),
+        HIP_TRY(launch_gauss_reduce(P, geom, recs, sums, flags, radii, live, live_count, stream, dL_dmean2D_abs),
                 "gauss_reduce");
     }
     if (int rc = check_debug(debug, stream, "gauss_reduce")) return rc;
@@ -1164,6 +1173,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
         if (atomic) {  // the sums are the accumulator rows of the touched Gaussians (render_bwd ATOMIC)
             ga.touched = geom.touched;
             ga.acc = geom.acc;
+            ga.dL_dmean2D_abs = dL_dmean2D_abs;
             // runs of 128 x N touched-bit positions per workgroup (backward.hip gauss_bwd_touched_kernel): N from
             // the option, or by the frame -- 16 where the lists are long (few Gaussians touched: 5M@4K), else 1
             const int opt_run = option(OPT_TOUCHED_RUN);
@@ -1284,6 +1294,26 @@ int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* backgr
                          dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, dc ? dL_ddc : nullptr,
                          dL_dsh, dL_dscale, dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream,
                          binning_capacity, binning_bytes, dL_dalphas);
+}
+
+int gsr_rasterize_backward_abs(int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                               const float* opacities, const float* scales, float scale_modifier,
+                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                               const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                               const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
+                               const float* dL_dpix, const float* dL_dinvdepths, const float* dL_dalphas,
+                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                               float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
+                               float* dL_dscale, float* dL_drot, int antialiasing, int debug,
+                               gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream, int binning_capacity,
+                               size_t binning_bytes, float* dL_dmean2D_abs) {
+    return backward_impl(P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
+                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
+                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, dc ? dL_ddc : nullptr,
+                         dL_dsh, dL_dscale, dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream,
+                         binning_capacity, binning_bytes, dL_dalphas, nullptr, dL_dmean2D_abs);
 }
 
 }  // extern "C"

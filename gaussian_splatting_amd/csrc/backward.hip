@@ -49,10 +49,14 @@ __device__ __forceinline__ uint64_t byte_flags(uint64_t x) {  // each nonzero by
     x |= x >> 1;
     return x & 0x0101010101010101ull;
 }
+// ABS: the records' two pad floats hold the absolute screen-space terms (render_bwd ABSGRAD); they are summed
+// as values 10 and 11 of the same scan into sd.  With ABS false the code is the one without them.
+template <bool ABS>
 __device__ __forceinline__ void reduce_records_compact(int P, int g0, const uint32_t* __restrict__ rec_start,
                                                        const uint32_t* __restrict__ tiles_touched,
                                                        const GradRecs& recs, float* s_rec, float4& sa, float4& sb,
-                                                       float2& sc) {
+                                                       float2& sc, float2& sd) {
+    constexpr int NV = ABS ? 12 : 10;
     const int lane = threadIdx.x;
     const int g = g0 + lane;
     const bool valid = g < P;
@@ -65,6 +69,7 @@ __device__ __forceinline__ void reduce_records_compact(int P, int g0, const uint
     sa = make_float4(0.f, 0.f, 0.f, 0.f);
     sb = sa;
     sc = make_float2(0.f, 0.f);
+    sd = sc;
     __shared__ uint16_t s_list[1024];  // the window's record positions, as offsets from its first byte
     __shared__ uint32_t s_mark[64];
     float4* part = reinterpret_cast<float4*>(s_rec);  // [64][3] float4: a Gaussian's group total
@@ -102,26 +107,29 @@ __device__ __forceinline__ void reduce_records_compact(int P, int g0, const uint
         // the next group's records are requested before this group is reduced (one latency per window
         // instead of one per group)
         float4 xn = make_float4(0.f, 0.f, 0.f, 0.f), yn = xn;
-        float2 zn = make_float2(0.f, 0.f);
+        float2 zn = make_float2(0.f, 0.f), wn = zn;  // (wn: ABS, the float2 behind c)
         if ((uint32_t)lane < R) {
             const uint32_t e = wa + (uint32_t)s_list[lane];
             xn = recs.a[(size_t)kRecAB * e];
             yn = recs.b[(size_t)kRecAB * e];
             zn = recs.c[(size_t)kRecC * e];
+            if (ABS) wn = recs.c[(size_t)kRecC * e + 1];
         }
         for (uint32_t k0 = 0; k0 < R; k0 += 64) {  // uniform: 64 records at a time
             const uint32_t k = k0 + (uint32_t)lane;
             const bool has = k < R;
             const float4 x = xn, y = yn;
-            const float2 z = zn;
+            const float2 z = zn, w2 = wn;
             if (k + 64 < R) {
                 const uint32_t e = wa + (uint32_t)s_list[k + 64];
                 xn = recs.a[(size_t)kRecAB * e];
                 yn = recs.b[(size_t)kRecAB * e];
                 zn = recs.c[(size_t)kRecC * e];
+                if (ABS) wn = recs.c[(size_t)kRecC * e + 1];
             } else {  // (lanes past the window's records: zeros, as unloaded lanes always held)
                 xn = yn = make_float4(0.f, 0.f, 0.f, 0.f);
                 zn = make_float2(0.f, 0.f);
+                wn = zn;
             }
             // owner of slot k: the largest lane with records whose first slot is <= k
             const unsigned long long st = __ballot(mine && r0 < k0);
@@ -140,9 +148,9 @@ __device__ __forceinline__ void reduce_records_compact(int P, int g0, const uint
                         m4 = lane - 4 >= seg0 && r >= 4 ? 1.f : 0.f, m8 = lane - 8 >= seg0 && r >= 8 ? 1.f : 0.f,
                         mb15 = (row & 1) && row * 16 - 1 >= seg0 ? 1.f : 0.f,
                         mb31 = row >= 2 && 31 >= seg0 ? 1.f : 0.f;
-            float v[10] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, z.x, z.y};
+            float v[12] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, z.x, z.y, w2.x, w2.y};
 #pragma unroll
-            for (int i = 0; i < 10; i++) {
+            for (int i = 0; i < NV; i++) {
                 v[i] = fmaf(dpp_f32<0x111, 0xf, true>(v[i]), m1, v[i]);
                 v[i] = fmaf(dpp_f32<0x112, 0xf, true>(v[i]), m2, v[i]);
                 v[i] = fmaf(dpp_f32<0x114, 0xf, true>(v[i]), m4, v[i]);
@@ -154,7 +162,7 @@ __device__ __forceinline__ void reduce_records_compact(int P, int g0, const uint
             if (owner >= 0 && (lane == 63 || next_owner != owner)) {  // the run's last lane hands it over
                 part[owner * 3 + 0] = make_float4(v[0], v[1], v[2], v[3]);
                 part[owner * 3 + 1] = make_float4(v[4], v[5], v[6], v[7]);
-                part[owner * 3 + 2] = make_float4(v[8], v[9], 0.f, 0.f);
+                part[owner * 3 + 2] = make_float4(v[8], v[9], ABS ? v[10] : 0.f, ABS ? v[11] : 0.f);
             }
             reduce_sync();
             if (max(r0, k0) < min(r1, k0 + 64)) {  // this Gaussian has records in the group
@@ -162,25 +170,31 @@ __device__ __forceinline__ void reduce_records_compact(int P, int g0, const uint
                 sa.x += pp.x; sa.y += pp.y; sa.z += pp.z; sa.w += pp.w;
                 sb.x += q.x; sb.y += q.y; sb.z += q.z; sb.w += q.w;
                 sc.x += ww.x; sc.y += ww.y;
+                if (ABS) { sd.x += ww.z; sd.y += ww.w; }
             }
             reduce_sync();
         }
     }
 }
 
+template <bool ABS>
 __global__ void __launch_bounds__(64) gauss_reduce_kernel(int P, const uint32_t* __restrict__ rec_start,
                                                           const uint32_t* __restrict__ tiles_touched,
                                                           GradRecs recs, GradRecs sums, uint32_t* __restrict__ flags,
                                                           const int* __restrict__ radii,
                                                           const uint8_t* __restrict__ clamped,
                                                           uint32_t* __restrict__ live,
-                                                          uint32_t* __restrict__ live_count, uint32_t live_cap) {
+                                                          uint32_t* __restrict__ live_count, uint32_t live_cap,
+                                                          float* __restrict__ abs_out) {
     __shared__ __attribute__((aligned(16))) float s_rec[64 * kRecStride];
     const int g = blockIdx.x * 64 + (int)threadIdx.x;
     const int rad = g < P ? radii[g] : 0;  // requested with the range loads, not after the reduction
     float4 sa, sb;
-    float2 sc;
-    reduce_records_compact(P, blockIdx.x * 64, rec_start, tiles_touched, recs, s_rec, sa, sb, sc);
+    float2 sc, sd;
+    reduce_records_compact<ABS>(P, blockIdx.x * 64, rec_start, tiles_touched, recs, s_rec, sa, sb, sc, sd);
+    // the absolute screen-space gradient [P,3]: every row written here (zeros for a Gaussian without records
+    // or culled), so it needs no zero fill and gauss_bwd does not touch it on this path
+    if (ABS && g < P) store3(abs_out, g, rad > 0 ? sd.x : 0.f, rad > 0 ? sd.y : 0.f, 0.f);
     // a Gaussian with a gradient (gauss_bwd's condition)
     const bool lv = g < P && rad > 0 &&
                     ((sa.x != 0.f) | (sa.y != 0.f) | (sa.z != 0.f) | (sa.w != 0.f) | (sb.x != 0.f) |
@@ -211,10 +225,16 @@ __global__ void __launch_bounds__(64) gauss_reduce_kernel(int P, const uint32_t*
 
 hipError_t launch_gauss_reduce(int P, const GeomState& g, const GradRecs& recs, const GradRecs& sums,
                                uint32_t* flags, const int* radii, uint32_t* live, uint32_t* live_count,
-                               hipStream_t stream) {
+                               hipStream_t stream, float* dL_dmean2D_abs) {
     if (P == 0) return hipSuccess;
-    hipLaunchKernelGGL(gauss_reduce_kernel, dim3((P + 63) / 64), dim3(64), 0, stream, P, g.rec_start, g.tiles_touched,
-                       recs, sums, flags, radii, g.clamped, live, live_count, live_list_cap((uint32_t)P));
+    if (dL_dmean2D_abs)
+        hipLaunchKernelGGL(gauss_reduce_kernel<true>, dim3((P + 63) / 64), dim3(64), 0, stream, P, g.rec_start,
+                           g.tiles_touched, recs, sums, flags, radii, g.clamped, live, live_count,
+                           live_list_cap((uint32_t)P), dL_dmean2D_abs);
+    else
+        hipLaunchKernelGGL(gauss_reduce_kernel<false>, dim3((P + 63) / 64), dim3(64), 0, stream, P, g.rec_start,
+                           g.tiles_touched, recs, sums, flags, radii, g.clamped, live, live_count,
+                           live_list_cap((uint32_t)P), dL_dmean2D_abs);
     return hipGetLastError();
 }
 
@@ -244,7 +264,9 @@ __device__ __forceinline__ void gb_sync() {
 // The rows of one wave: Gaussians g0 + lane (dense), or each lane's idx (LIST; a.P: none).  TOUCHED (the
 // atomic backward): the sums are the accumulator rows render_bwd added into, read and zeroed here.
 constexpr int kGbShFloats = kGbShRows * kShStride;  // one wave's SH staging (LDS)
-template <int SH_MODE, bool LIST, bool TOUCHED>
+// ABS (TOUCHED only): floats 10, 11 of the row are the summed |dL/dmean2D| terms (render_bwd ABSGRAD) and go to
+// GaussBwdArgs::dL_dmean2D_abs; a compile-time variant, so the kernels without it are the ones before it.
+template <int SH_MODE, bool LIST, bool TOUCHED, bool ABS = false>
 __device__ __forceinline__ void gauss_bwd_rows(const GaussBwdArgs& a, const int g0, const int idx, float* s_sh) {
     const int lane = threadIdx.x & 63;
     const int nvalid = min(64, a.P - g0);
@@ -273,6 +295,8 @@ __device__ __forceinline__ void gauss_bwd_rows(const GaussBwdArgs& a, const int 
             sb = row[1];
             const float4 c4 = row[2];
             sc = make_float2(c4.x, c4.y);
+            // a touched row is a visible Gaussian's; the rows of the others were zero-filled with the dense outputs
+            if constexpr (ABS) store3(a.dL_dmean2D_abs, idx, c4.z, c4.w, 0.f);
         } else {  // (record path: gauss_reduce's per-Gaussian sums)
             sa = a.sums.a[idx];
             sb = a.sums.b[idx];
@@ -457,7 +481,7 @@ constexpr uint32_t kTouchedShiftMax = 5;         // at most 32 sub-runs per work
 constexpr uint32_t kTouchedRing = 2 * kTouchedSub;
 static_assert((kTouchedSub << kTouchedShiftMax) / 32 == kTouchedSub, "one touched word per thread at most");
 static_assert(kTouchedRing >= 2 * kTouchedSub, "the ring holds an unflushed rest plus one sub-run");
-template <int SH_MODE, bool RUNS>
+template <int SH_MODE, bool RUNS, bool ABS = false>
 __global__ void __launch_bounds__(64 * kTouchedWaves) gauss_bwd_touched_kernel(GaussBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float s_sh[kTouchedWaves][SH_MODE != kShGlobal ? kGbShFloats : 4];
     __shared__ uint32_t s_list[RUNS ? kTouchedRing : kTouchedSub];
@@ -483,7 +507,7 @@ __global__ void __launch_bounds__(64 * kTouchedWaves) gauss_bwd_touched_kernel(G
         const uint32_t k0 = 64u * (uint32_t)wave;
         if (k0 >= total) return;  // uniform per wave
         const int idx = k0 + (uint32_t)lane < total ? (int)s_list[k0 + lane] : a.P;
-        gauss_bwd_rows<SH_MODE, true, true>(a, 0, idx, s_sh[wave]);
+        gauss_bwd_rows<SH_MODE, true, true, ABS>(a, 0, idx, s_sh[wave]);
     } else {
         const int nsub = 1 << a.touched_shift;
         const uint32_t run0 = blockIdx.x * ((uint32_t)kTouchedSub << a.touched_shift);
@@ -523,7 +547,7 @@ __global__ void __launch_bounds__(64 * kTouchedWaves) gauss_bwd_touched_kernel(G
                 const uint32_t k0 = 64u * (uint32_t)wave;
                 if (k0 < n) {  // uniform per wave
                     const int idx = k0 + (uint32_t)lane < n ? (int)s_list[(head + k0 + lane) % kTouchedRing] : a.P;
-                    gauss_bwd_rows<SH_MODE, true, true>(a, 0, idx, s_sh[wave]);
+                    gauss_bwd_rows<SH_MODE, true, true, ABS>(a, 0, idx, s_sh[wave]);
                 }
                 head += n;
             }
@@ -562,7 +586,16 @@ hipError_t launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t stream) {
         const dim3 tgrid((uint32_t)(((size_t)a.P + run - 1) / run)), tblock(64 * kTouchedWaves);
         const bool runs = a.touched_shift > 0;
         void (*k)(GaussBwdArgs);
-        if (lds_ok && a.dc)
+        if (a.dL_dmean2D_abs) {
+            if (lds_ok && a.dc)
+                k = runs ? gauss_bwd_touched_kernel<kShLdsSplit, true, true>
+                         : gauss_bwd_touched_kernel<kShLdsSplit, false, true>;
+            else if (lds_ok)
+                k = runs ? gauss_bwd_touched_kernel<kShLdsCombined, true, true>
+                         : gauss_bwd_touched_kernel<kShLdsCombined, false, true>;
+            else
+                k = runs ? gauss_bwd_touched_kernel<kShGlobal, true, true> : gauss_bwd_touched_kernel<kShGlobal, false, true>;
+        } else if (lds_ok && a.dc)
             k = runs ? gauss_bwd_touched_kernel<kShLdsSplit, true> : gauss_bwd_touched_kernel<kShLdsSplit, false>;
         else if (lds_ok)
             k = runs ? gauss_bwd_touched_kernel<kShLdsCombined, true> : gauss_bwd_touched_kernel<kShLdsCombined, false>;

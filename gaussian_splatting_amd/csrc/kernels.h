@@ -114,6 +114,10 @@ struct RenderBwdArgs {
     // seed of the per-pixel scalar gB beside the background term, whose form it shares (non-null selects
     // render_bwd's ALPHA instantiations; the others never read it)
     const float* dL_dalpha;
+    // absolute screen-space gradient (gsr_rasterize_backward_abs): non-zero selects render_bwd's ABSGRAD
+    // instantiations, which also sum each entry's per-pixel |dL/dmean2D| terms -- into floats 10, 11 of the
+    // accumulator row (atomic), or the record's two pad floats.  Not with the census.
+    int absgrad;
 };
 
 struct GaussBwdArgs {
@@ -153,6 +157,10 @@ struct GaussBwdArgs {
     uint32_t* touched;           // atomic backward (sparse): the touched bits render_bwd set, or null; cleared here
     float4* acc;                 // with touched: the accumulator rows (the sums), zeroed after reading
     uint32_t touched_shift;      // with touched: a workgroup lists 128 << touched_shift Gaussians ("touched_run")
+    // [P,3] absolute screen-space gradient, or null.  Atomic backward only: floats 10, 11 of each touched row
+    // (render_bwd ABSGRAD), the other rows zero-filled with the dense outputs.  On the record path
+    // gauss_reduce writes every row of it and this stays null.
+    float* dL_dmean2D_abs;
 };
 
 hipError_t launch_zero_fill(const FillArgs& f, hipStream_t stream);
@@ -445,9 +453,11 @@ size_t bwd_max_units(size_t R, uint32_t tiles, int seg_ck);
 // Longest reachable prefix K4 sorts ("sort_prefix" option range; binning.hip kPrefixBuf holds twice it).
 constexpr uint32_t kSortPrefixMax = 1024;
 // backward.hip
+// dL_dmean2D_abs ([P,3] or null): the records carry the absolute screen-space terms (render_bwd ABSGRAD) and
+// their per-Gaussian sums are written there, every row, in the same fixed order as the other sums
 hipError_t launch_gauss_reduce(int P, const GeomState& g, const GradRecs& recs, const GradRecs& sums,
                                uint32_t* flags, const int* radii, uint32_t* live, uint32_t* live_count,
-                               hipStream_t stream);
+                               hipStream_t stream, float* dL_dmean2D_abs = nullptr);
 hipError_t launch_gauss_bwd(const GaussBwdArgs& a, hipStream_t stream);
 // views.hip (the two launchers the screen-space backward of api.hip's backward_impl fills a view block with)
 // atomic screen-space backward: the view block's dense sums (a touched Gaussian's row, zeroed after; zeros

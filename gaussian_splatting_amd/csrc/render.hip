@@ -506,7 +506,7 @@ hipError_t launch_render_fwd(const RenderFwdArgs& a, hipStream_t stream, int qua
 // instead of a 48-byte record at the instance's emission index for gauss_reduce to sum: no record
 // writes, no record-start gathers, no gauss_reduce.  The flush compacts the batch's written entries
 // into an LDS list and issues one wave instruction per FOUR entries -- lane 16k + v adds value v
-// (< 10) of listed entry k -- so an instruction touches four 64-byte rows, the shape the memory-side
+// (< 10; < 12 with ABSGRAD) of listed entry k -- so an instruction touches four 64-byte rows, the shape the memory-side
 // atomic units take at full rate (MI355X_MICROARCH.md "Global float atomics": 64 lanes in 64 rows
 // run ~17x slower).  The summation order over a Gaussian's instances then follows the hardware, so
 // the result is not bitwise reproducible; the record path (bwd_atomic=0) is.  The default since r5f:
@@ -517,7 +517,15 @@ hipError_t launch_render_fwd(const RenderFwdArgs& a, hipStream_t stream, int qua
 // a scalar branch around it, and four more of those in every unit cost a backward with no alpha gradient
 // +0.28% of the 1M@1080p step (0.6919 -> 0.6938 ms over ten interleaved pairs).  With
 // ALPHA false the kernel is the one without the feature.
-template <bool CENSUS, bool STRIDED, bool ATOMIC, bool ALPHA>
+// ABSGRAD (RenderBwdArgs::absgrad, chosen by the launcher like ALPHA): two more per-entry sums, the absolute
+// values of the pixel's terms of dL/dmean2D (CR/backward.cu:600-601), summed over the pixels:
+//   r10 = sum |udx A + udy B/2|, r11 = sum |udx B/2 + udy C|  (A, B, C the staged conic: -log2e / 2 times a, b, c)
+// |k x| = |k| |x|, so the per-pixel factor is the staged conic alone and the flush applies W o / log2e (H o / log2e)
+// once per entry.  They are folded like r8 / r9 into a fourth plane of s_acc (row partials), land behind dconic
+// in the entry's final form -- accumulator row floats 10, 11 (zero otherwise), the record's two pad floats -- and
+// gauss_bwd / gauss_reduce turn them into the [P,3] output (include/gsr.h gsr_rasterize_backward_abs).  With
+// ABSGRAD false the generated code is that of the kernel without the feature.
+template <bool CENSUS, bool STRIDED, bool ATOMIC, bool ALPHA, bool ABSGRAD = false>
 __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
   {
     // One wave per unit = (tile, segment): the entries [start, end) of the tile's list, start a
@@ -567,8 +575,9 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
     __shared__ float4 s_xy[kBatch], s_cq[kBatch], s_col[kBatch];  // as in the forward
     // per entry: the 10 reduced sums (r8, r9 in 2 parts), three float4 planes indexed by entry like the
     // staged rows, so a reduction's store address is the entry's row offset (already scalar for the
-    // row reads) plus a per-lane constant (an [entry][3] layout cost a quarter-rate v_mad_u64_u32)
-    __shared__ float4 s_acc[3][kBatch];
+    // row reads) plus a per-lane constant (an [entry][3] layout cost a quarter-rate v_mad_u64_u32).
+    // ABSGRAD: a fourth plane for the row partials of r10, r11 (plane 2 is full until the flush).
+    __shared__ float4 s_acc[ABSGRAD ? 4 : 3][kBatch];
     __shared__ uint32_t s_wgid[ATOMIC ? kBatch : 1], s_wj[ATOMIC ? kBatch : 1];  // ATOMIC: written entries' Gaussian, slot
     GSR_STAMP(g_st_rbwd, blockIdx.x, 0);
     GSR_STAMP_HWID(g_st_rbwd, blockIdx.x);
@@ -703,6 +712,8 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
             const uint32_t m = uniform_u32(__float_as_uint(cq.w)) & live;
             if (m == 0) continue;
             float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f, r4 = 0.f, r5 = 0.f, r6 = 0.f, r7 = 0.f, r8 = 0.f, r9 = 0.f;
+            float r10 = 0.f, r11 = 0.f;       // ABSGRAD only
+            const float hb = 0.5f * cq.y;     // ABSGRAD only: the staged B is the exponent's 2 b term
             bool contrib = false;
 #pragma unroll
             for (int q = 0; q < 4; q++) {
@@ -739,6 +750,10 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
                 r7 += udx * dy;
                 r8 += udy * dy;
                 r9 += u;
+                if (ABSGRAD) {  // this pixel's |dL/dmean2D| terms, up to the entry's positive factor (the flush)
+                    r10 += fabsf(udx * cq.x + udy * hb);
+                    r11 += fabsf(udx * hb + udy * cq.z);
+                }
                 T[q] *= one_m_a;  // alpha = 0 leaves T unchanged
             }
             if (contrib) {  // uniform
@@ -752,6 +767,10 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
                 const float f = half_row_allsum(eight_fold(row_fold(h0, h1), row_fold(h2, h3), hi8));
                 const float g4 = row_allsum(h4);
                 if (acc_wr) reinterpret_cast<float*>(s_acc)[j * 4 + acc_lane] = acc_h4 ? g4 : f;
+                if (ABSGRAD) {  // rows of h5: r10 r10 r11 r11, beside h4's in the next plane
+                    const float g5 = row_allsum(half_fold(r10, r11));
+                    if (acc_h4) reinterpret_cast<float*>(s_acc)[j * 4 + acc_lane + 4 * kBatch] = g5;
+                }
                 written |= 1ull << j;
                 if (CENSUS) c_red++;
             }
@@ -765,7 +784,14 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
                 const float s8 = Cc.x + Cc.y, s9 = Cc.z + Cc.w;
                 s_acc[1][lane] = make_float4(-0.5f * (float)a.W * o * (ca * B.x + cb * B.y),
                                              -0.5f * (float)a.H * o * (cc * B.y + cb * B.x), s9, -0.5f * o * B.w);
-                s_acc[2][lane] = make_float4(-0.5f * o * B.z, -0.5f * o * s8, 0.f, 0.f);
+                float ax = 0.f, ay = 0.f;  // ABSGRAD: |o| / log2e x (W, H) x the summed absolute terms
+                if (ABSGRAD) {
+                    const float4 D = s_acc[ABSGRAD ? 3 : 0][lane];
+                    const float k = fabsf(o) * (1.0f / kLog2e);
+                    ax = (float)a.W * k * (D.x + D.y);
+                    ay = (float)a.H * k * (D.z + D.w);
+                }
+                s_acc[2][lane] = make_float4(-0.5f * o * B.z, -0.5f * o * s8, ax, ay);
                 (void)A;  // (row a is stored as reduced)
                 const int slot = __popcll(written & ((1ull << lane) - 1ull));
                 s_wgid[slot] = e;
@@ -778,7 +804,7 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
             const int nw = __popcll(written), sub = lane >> 4, v = lane & 15;
             for (int k0 = 0; k0 < nw; k0 += 4) {  // uniform
                 const int k = k0 + sub;
-                if (k < nw && v < 10) {
+                if (k < nw && v < (ABSGRAD ? 12 : 10)) {
                     const int j = (int)s_wj[k];
                     const float val = reinterpret_cast<const float*>(s_acc)[(v >> 2) * (4 * kBatch) + j * 4 + (v & 3)];
                     (void)atomicAdd(a.acc + (size_t)s_wgid[k] * (4 * kAccRow4) + v, val);  // (no return: fire and forget)
@@ -787,7 +813,7 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
         } else if (has && content) {
             (void)atomicOr(reinterpret_cast<uint32_t*>(a.recs.flag) + (e >> 5), 1u << (e & 31u));
             float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-            float2 rc = make_float2(0.f, 0.f);
+            float2 rc = make_float2(0.f, 0.f), rd = rc;  // (rd: ABSGRAD, else the record's pad)
             if (content) {
                 const float4 A = s_acc[0][lane], B = s_acc[1][lane], Cc = s_acc[2][lane];
                 // dL/dmean2D in NDC units (x 0.5 W, 0.5 H, CR/backward.cu:509-510,600-601);
@@ -798,12 +824,17 @@ __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {
                 rb = make_float4(-0.5f * (float)a.W * o * (ca * B.x + cb * B.y),
                                  -0.5f * (float)a.H * o * (cc * B.y + cb * B.x), s9, -0.5f * o * B.w);
                 rc = make_float2(-0.5f * o * B.z, -0.5f * o * s8);
+                if (ABSGRAD) {  // |o| / log2e x (W, H) x the summed absolute terms
+                    const float4 D = s_acc[ABSGRAD ? 3 : 0][lane];
+                    const float k = fabsf(o) * (1.0f / kLog2e);
+                    rd = make_float2((float)a.W * k * (D.x + D.y), (float)a.H * k * (D.z + D.w));
+                }
             }
             // one 48-byte record (a, b, c + pad at recs.a + 0/1/2): one address, full-width stores
             float4* r = a.recs.a + (size_t)kRecAB * e;
             r[0] = ra;
             r[1] = rb;
-            r[2] = make_float4(rc.x, rc.y, 0.f, 0.f);
+            r[2] = make_float4(rc.x, rc.y, rd.x, rd.y);
         }
         unit_sync();
     }
@@ -829,7 +860,12 @@ size_t bwd_max_units(size_t R, uint32_t tiles, int seg_ck) { return R / ((size_t
 
 template <bool ATOMIC, bool ALPHA>
 static void launch_render_bwd_t(const RenderBwdArgs& a, uint32_t grid, bool strided, hipStream_t stream) {
-    if (a.census)
+    if (a.absgrad) {  // (never with the census: launch_render_bwd refuses the pair)
+        if (strided)
+            hipLaunchKernelGGL((render_bwd_kernel<false, true, ATOMIC, ALPHA, true>), dim3(grid), dim3(kWave), 0, stream, a);
+        else
+            hipLaunchKernelGGL((render_bwd_kernel<false, false, ATOMIC, ALPHA, true>), dim3(grid), dim3(kWave), 0, stream, a);
+    } else if (a.census)
         hipLaunchKernelGGL((render_bwd_kernel<true, false, ATOMIC, ALPHA>), dim3(grid), dim3(kWave), 0, stream, a);
     else if (strided)
         hipLaunchKernelGGL((render_bwd_kernel<false, true, ATOMIC, ALPHA>), dim3(grid), dim3(kWave), 0, stream, a);
@@ -842,6 +878,7 @@ static void launch_render_bwd_t(const RenderBwdArgs& a, uint32_t grid, bool stri
 constexpr uint32_t kBwdGridTiles = 2, kBwdStrideRatio = 4;
 hipError_t launch_render_bwd(const RenderBwdArgs& a, size_t max_units, hipStream_t stream, int grid_mode) {
     if (max_units == 0) return hipSuccess;
+    if (a.absgrad && a.census) return hipErrorInvalidValue;  // (no CENSUS x ABSGRAD instantiation; api.hip checks first)
     const size_t strided_units = std::min(max_units, (size_t)kBwdGridTiles * a.gx * a.gy);
     const bool strided = !a.census && (grid_mode == 2 || (grid_mode == 0 && max_units > kBwdStrideRatio * strided_units));
     const uint32_t grid = (uint32_t)(strided ? strided_units : max_units) + a.fill_blocks;  // fill blocks first

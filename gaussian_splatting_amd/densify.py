@@ -126,11 +126,22 @@ def _filter_mask(update_filter: torch.Tensor, P: int, device) -> torch.Tensor:
     return m
 
 
-def add_densification_stats(model, viewspace_point_tensor, update_filter) -> None:
-    """``GaussianModel.add_densification_stats`` (gaussian_model.py:643-654)."""
+def add_densification_stats(model, viewspace_point_tensor, update_filter, absgrad: bool = False) -> None:
+    """``GaussianModel.add_densification_stats`` (gaussian_model.py:643-654).
+
+    ``absgrad=True`` (an extension, AbsGS): accumulates ``||viewspace_point_tensor.absgrad[v, :2]||``, the absolute
+    screen-space gradient the backward of a render with ``absgrad=True`` set on the tensor, instead of the norm
+    of ``.grad``."""
+    if absgrad:
+        grad = getattr(viewspace_point_tensor, "absgrad", None)
+        if grad is None:
+            raise RuntimeError("add_densification_stats(absgrad=True): the viewspace tensor has no .absgrad -- render "
+                               "with absgrad=True and run the backward first")
+    else:
+        grad = viewspace_point_tensor.grad
     P = model.xyz_gradient_accum.shape[0]
     mask = _filter_mask(update_filter, P, model.xyz_gradient_accum.device)
-    densification_stats(viewspace_point_tensor.grad, model.xyz_gradient_accum, model.denom, visible=mask)
+    densification_stats(grad, model.xyz_gradient_accum, model.denom, visible=mask)
 
 
 def update_max_radii(model, radii: torch.Tensor, visibility_filter=None) -> None:

@@ -40,15 +40,21 @@ class GaussianRasterizationSettings(NamedTuple):
     antialiasing: bool
 
 
-def rasterize_gaussians(*args, return_alpha=False):
+def rasterize_gaussians(*args, return_alpha=False, absgrad=False):
     """``rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
     raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``.
 
     ``return_alpha=True`` (an extension): returns ``(color, radii, invdepths, alpha)``, ``alpha`` [1,H,W] the
-    accumulated opacity ``1 - final_T`` of every pixel, differentiable like the other two maps."""
+    accumulated opacity ``1 - final_T`` of every pixel, differentiable like the other two maps.
+
+    ``absgrad=True`` (an extension, gsplat's convention): the backward of this render also sets
+    ``means2D.absgrad`` [P,3] (float32, on the device): per Gaussian the sum over pixels of the ABSOLUTE value of
+    each pixel's term of ``means2D.grad`` (AbsGS; include/gsr.h gsr_rasterize_backward_abs), column 2 zero.  Each
+    backward overwrites it.  Without the keyword no attribute is set and nothing more is launched or allocated."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
     _RasterizeGaussians._return_alpha.value = bool(return_alpha)  # (read and cleared by the node's forward)
+    _RasterizeGaussians._absgrad.value = bool(absgrad)            # (likewise)
     # Camera-pose gradients: when a camera tensor of the settings requires grad (and grad mode is on) the three
     # enter the autograd node as explicit inputs after the settings; every other render takes the path below.
     s = args[-1]
@@ -76,6 +82,21 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     _no_backward = threading.local()
     _return_alpha = threading.local()  # set by rasterize_gaussians(..., return_alpha=True) for its one call
+    _absgrad = threading.local()       # set by rasterize_gaussians(..., absgrad=True) for its one call
+
+    @staticmethod
+    def _absgrad_kw(ctx):
+        """``{"absgrad": True}`` for a node rendered with the keyword, else no keyword at all."""
+        return {} if ctx.absgrad_of is None else {"absgrad": True}
+
+    @staticmethod
+    def _set_absgrad(ctx, grads):
+        """Takes the absolute gradient (last) off the backward's tuple of an absgrad node and sets it on the
+        node's means2D, overwriting that of an earlier backward."""
+        if ctx.absgrad_of is None:
+            return grads
+        ctx.absgrad_of.absgrad = grads[-1]
+        return grads[:-1]
 
     @staticmethod
     def _upstream(ctx, grad_out_color, grad_out_depth, grad_alpha):
@@ -109,6 +130,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         with_alpha = getattr(_RasterizeGaussians._return_alpha, "value", False)
         _RasterizeGaussians._return_alpha.value = False
         ctx.with_alpha = with_alpha
+        # absgrad: the node keeps means2D (its value is never read) and its backward sets means2D.absgrad
+        ctx.absgrad_of = means2D if getattr(_RasterizeGaussians._absgrad, "value", False) else None
+        _RasterizeGaussians._absgrad.value = False
         if with_alpha:
             num_rendered, color, radii, geom, binning, img, invdepths, alpha = _C.rasterize_gaussians(
                 *head, *sh_args, *tail, no_backward=no_backward, return_alpha=True)
@@ -142,12 +166,14 @@ class _RasterizeGaussians(torch.autograd.Function):
 
         if dc is None:
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*head, sh, *tail, **alpha_kw)
+             grad_scales, grad_rotations) = _RasterizeGaussians._set_absgrad(ctx, _C.rasterize_gaussians_backward(
+                 *head, sh, *tail, **alpha_kw, **_RasterizeGaussians._absgrad_kw(ctx)))
             return (grad_means3D, grad_means2D, fit(grad_sh, sh), fit(grad_colors_precomp, colors_precomp),
                     grad_opacities, fit(grad_scales, scales), fit(grad_rotations, rotations),
                     fit(grad_cov3Ds_precomp, cov3Ds_precomp), None)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_dc, grad_sh,
-         grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*head, dc, sh, *tail, **alpha_kw)
+         grad_scales, grad_rotations) = _RasterizeGaussians._set_absgrad(ctx, _C.rasterize_gaussians_backward(
+             *head, dc, sh, *tail, **alpha_kw, **_RasterizeGaussians._absgrad_kw(ctx)))
         return (grad_means3D, grad_means2D, fit(grad_dc, dc), fit(grad_sh, sh),
                 fit(grad_colors_precomp, colors_precomp), grad_opacities, fit(grad_scales, scales),
                 fit(grad_rotations, rotations), fit(grad_cov3Ds_precomp, cov3Ds_precomp), None)
@@ -179,8 +205,8 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
                 view, proj, s.tanfovx, s.tanfovy, grad_out_color, grad_out_depth)
         tail = (s.sh_degree, campos, geom, ctx.num_rendered, binning, img, s.antialiasing, s.debug)
         sh_args = (sh,) if dc is None else (dc, sh)
-        *grads, g_view, g_proj, g_campos = _C.rasterize_gaussians_backward(*head, *sh_args, *tail, camera=True,
-                                                                            **alpha_kw)
+        *grads, g_view, g_proj, g_campos = _RasterizeGaussians._set_absgrad(ctx, _C.rasterize_gaussians_backward(
+            *head, *sh_args, *tail, camera=True, **alpha_kw, **_RasterizeGaussians._absgrad_kw(ctx)))
 
         def fit(g, like):  # inputs given as empty tensors get no gradient
             return None if like is None or like.numel() == 0 else g
@@ -214,11 +240,12 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None, return_alpha=False):
+                cov3D_precomp=None, dc=None, return_alpha=False, absgrad=False):
         """Same checks as the reference (:242-261).  ``dc=`` (keyword) selects the 3DGS-accel separate-SH
         input: ``dc`` = ``_features_dc`` [P,1,3] and ``shs`` = ``_features_rest`` [P,M,3]
         (gaussian_renderer/__init__.py:115-125).  ``return_alpha=True`` returns ``(color, radii, invdepths,
-        alpha)`` with the differentiable accumulated-alpha map [1,H,W] (``rasterize_gaussians``)."""
+        alpha)`` with the differentiable accumulated-alpha map [1,H,W] (``rasterize_gaussians``).
+        ``absgrad=True``: the backward also sets ``means2D.absgrad`` (``rasterize_gaussians``)."""
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -233,7 +260,7 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
         if dc is None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, s, return_alpha=return_alpha)
+                                       cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad)
         dc = empty if colors_precomp.numel() != 0 else dc
         return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, s, return_alpha=return_alpha)
+                                   cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad)

@@ -196,6 +196,35 @@ int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* backgr
                                  float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
                                  void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes);
 
+/* Absolute screen-space gradient (the densification statistic of AbsGS; gsplat's absgrad).
+ * dL_dmean2D is a signed sum over pixels, so the per-pixel terms of a large Gaussian cancel across its
+ * centre; the absolute value has to be taken per pixel, inside the render backward.
+ *
+ * gsr_rasterize_backward_abs: gsr_rasterize_backward_alpha with one more output dL_dmean2D_abs ([P,3], may
+ *   be NULL: then exactly gsr_rasterize_backward_alpha).  For Gaussian g
+ *     dL_dmean2D_abs[g] = (sum_pix |t_x(g, pix)|, sum_pix |t_y(g, pix)|, 0),
+ *   t_x, t_y the terms the reference adds per pixel into dL_dmean2D (CR/backward.cu:600-601), in the same
+ *   NDC units (x 0.5 W, 0.5 H).  A pixel's term is its total over all upstream maps (colour, inverse depth
+ *   and, when given, alpha), the sum runs over every tile instance of the Gaussian, and the skip tests, early
+ *   termination, 0.99 clamp and antialiasing are those of dL_dmean2D.  Every element is written; rows with
+ *   radii == 0 are zero, and P == 0 or R == 0 gives zeros.  Every other output is what
+ *   gsr_rasterize_backward_alpha writes (bitwise on the record path, "bwd_atomic" 0, where dL_dmean2D_abs is
+ *   bitwise reproducible too).  GSR_ERR_ARGUMENT when the census is set (gsr_census_set): the census form
+ *   of the render backward has no absolute-gradient variant.  Not supported: the multi-GPU view blocks
+ *   (gsr_rasterize_backward_screen and the view exchange carry no absolute gradient). */
+int gsr_rasterize_backward_abs(int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                               const float* opacities, const float* scales, float scale_modifier,
+                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                               const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                               const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
+                               const float* dL_dpix, const float* dL_dinvdepths, const float* dL_dalphas,
+                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                               float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
+                               float* dL_dscale, float* dL_drot, int antialiasing, int debug,
+                               gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream, int binning_capacity,
+                               size_t binning_bytes, float* dL_dmean2D_abs);
+
 /* Multi-GPU view exchange (gaussian_splatting_amd/distributed.py
  * ViewExchange).  The reference trains on one GPU; sharding views over N ranks needs the
  * N views' parameter gradients summed on every rank.  Instead of all-reducing the 59-float
