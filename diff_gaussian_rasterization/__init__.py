@@ -13,6 +13,7 @@ reference's signatures.  Both interfaces the reference's callers can meet are se
   only the visible Gaussians (train.py:240-246).
 """
 from gaussian_splatting_amd import _C  # noqa: F401
+from gaussian_splatting_amd.contrib import ContributionStats, render_contribution, split  # noqa: F401
 from gaussian_splatting_amd.optim import SparseGaussianAdam  # noqa: F401
 from gaussian_splatting_amd.rasterizer import (  # noqa: F401
     GaussianRasterizationSettings,
@@ -23,4 +24,4 @@ from gaussian_splatting_amd.rasterizer import (  # noqa: F401
 )
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "SparseGaussianAdam", "cpu_deep_copy_tuple", "_C"]
+           "SparseGaussianAdam", "cpu_deep_copy_tuple", "_C", "ContributionStats", "split", "render_contribution"]

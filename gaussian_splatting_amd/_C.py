@@ -25,7 +25,7 @@ __all__ = ["rasterize_gaussians", "rasterize_gaussians_backward", "rasterize_gau
            "gauss_backward_views", "view_block_floats", "view_pack_floats", "view_block_pack", "view_block_unpack", "view_block_index",
            "views_live_floats", "views_live_list",
            "mark_visible", "adamUpdate", "fusedssim",
-           "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha"]
+           "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha", "contribution_stats"]
 
 
 # Sync-free forward (gsr_rasterize_forward_ex): the binning buffer is sized from a capacity
@@ -176,6 +176,44 @@ def render_alpha(imgBuffer: torch.Tensor, image_height: int, image_width: int) -
         rc = _lib.load().gsr_render_alpha(W, H, imgBuffer.data_ptr(), alpha.data_ptr(), _stream_handle(device))
     _lib.check(rc, "render_alpha")
     return alpha
+
+
+def contribution_stats(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imgBuffer: torch.Tensor,
+                       num_rendered: int, P: int, image_height: int, image_width: int,
+                       pixel_weight: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-Gaussian contribution statistics [P,4] float32 of the forward that filled the three buffers (include/gsr.h
+    gsr_contrib_stats), on the current stream: columns ``weight_sum``, ``weight_max``, ``pixel_count`` (uint32 bits:
+    view the column as int32) and ``weighted_sum`` (the blend weights times ``pixel_weight`` [H,W] or [1,H,W]; zero
+    without it).  With ``out`` (contiguous float32 [P,4]) the view's statistics are combined into it -- sums and
+    counts add, the maximum maxes -- and it is returned.  Read-only on the buffers (copies are accepted, a backward
+    may precede or follow); not differentiable."""
+    P, H, W = int(P), int(image_height), int(image_width)
+    device = geomBuffer.device
+    f32 = dict(dtype=torch.float32, device=device)
+    if out is not None:
+        if (tuple(out.shape) != (P, 4) or out.dtype != torch.float32 or not out.is_contiguous()
+                or out.device != device):
+            raise RuntimeError(f"out must be a contiguous float32 {(P, 4)} tensor on {device}")
+    pw = None
+    if pixel_weight is not None:
+        if tuple(pixel_weight.shape) not in ((H, W), (1, H, W)):
+            raise RuntimeError(f"pixel_weight: expected {(H, W)} or {(1, H, W)}, got {tuple(pixel_weight.shape)}")
+        if pixel_weight.dtype != torch.float32:
+            raise RuntimeError(f"pixel_weight: expected a float32 tensor, got {pixel_weight.dtype}")
+        pw = pixel_weight.detach().to(device).contiguous()
+    if P == 0:
+        return out if out is not None else torch.zeros((0, 4), **f32)
+    _require_device(geomBuffer, "geomBuffer")
+    stats = out if out is not None else _empty((P, 4), **f32)  # every row is written
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_contrib_stats(
+            P, int(num_rendered), W, H, geomBuffer.data_ptr() if geomBuffer.numel() else None,
+            binningBuffer.data_ptr() if binningBuffer.numel() else None,
+            imgBuffer.data_ptr() if imgBuffer.numel() else None, 0, int(binningBuffer.numel()),
+            pw.data_ptr() if pw is not None else None, int(out is not None), stats.data_ptr(),
+            _stream_handle(device))
+    _lib.check(rc, "contribution_stats")
+    return stats
 
 
 def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = False) -> tuple:

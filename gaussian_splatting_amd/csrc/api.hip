@@ -303,23 +303,27 @@ struct GeomMark {
     const void* buf;
     bool zeroed, recs;
     bool long_lists;  // the frame's mean tile list is long (kLongMeanList): few of its Gaussians are touched
+    // the render ran as half-tile / quadrant units (not the whole-tile kernel of "fwd_quads" 4): the T in its blend
+    // checkpoints rounds as contrib.hip's own (gsr_contrib_stats)
+    bool half_fwd;
 };
 std::mutex g_mark_mu;
 std::vector<GeomMark> g_marks;
 constexpr size_t kGeomMarksMax = 4096;
 
-void geom_mark(const void* geom_buffer, bool zeroed, bool recs, bool long_lists) {
+void geom_mark(const void* geom_buffer, bool zeroed, bool recs, bool long_lists, bool half_fwd) {
     std::lock_guard<std::mutex> lk(g_mark_mu);
     for (auto& m : g_marks)
         if (m.buf == geom_buffer) {
             m.zeroed = zeroed;
             m.recs = recs;
             m.long_lists = long_lists;
+            m.half_fwd = half_fwd;
             return;
         }
     if (!zeroed && !recs) return;  // (absent = neither)
     if (g_marks.size() >= kGeomMarksMax) g_marks.clear();
-    g_marks.push_back(GeomMark{geom_buffer, zeroed, recs, long_lists});
+    g_marks.push_back(GeomMark{geom_buffer, zeroed, recs, long_lists, half_fwd});
 }
 
 void geom_forget(const void* geom_buffer) {
@@ -336,7 +340,7 @@ GeomMark geom_marked(const void* geom_buffer) {
     std::lock_guard<std::mutex> lk(g_mark_mu);
     for (const auto& m : g_marks)
         if (m.buf == geom_buffer) return m;
-    return GeomMark{geom_buffer, false, false, false};
+    return GeomMark{geom_buffer, false, false, false, false};
 }
 
 // A frame whose mean tile list holds at least this many entries is a "long-list" frame: near-first binning
@@ -679,7 +683,7 @@ int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_a
     char* gbase = (char*)call_alloc(geom_alloc, geom_ctx, geom_bytes);
     if (!gbase) return fail(GSR_ERR_ALLOC, "rasterize_forward: geometry buffer allocation failed");
     GeomState geom = carve_geom(gbase, P, gx, gy, &geom_bytes);
-    geom_mark(gbase, false, false, false);  // (set below once the binning and the render's fill blocks are queued)
+    geom_mark(gbase, false, false, false, false);  // (set below once the binning and the render's fill blocks are queued)
     carve_image(nullptr, width, height, tiles, &img_bytes);
     char* ibase = (char*)call_alloc(image_alloc, image_ctx, img_bytes);
     if (!ibase) return fail(GSR_ERR_ALLOC, "rasterize_forward: image buffer allocation failed");
@@ -834,7 +838,9 @@ int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_a
                 ra.fill_blocks = kFwdFillBlocks;
             }
             HIP_TRY(launch_render_fwd(ra, stream, opt_quads), "render_fwd");
-            geom_mark(gbase, opt_atomic, k3_recs, (size_t)C >= kLongMeanList * (size_t)tiles);
+            // (launch_render_fwd: the whole-tile kernel runs for fwd_quads = 4 without the census only)
+            geom_mark(gbase, opt_atomic, k3_recs, (size_t)C >= kLongMeanList * (size_t)tiles,
+                      !(opt_quads == 4 && !g_census));
             const bool near_now = fused_now && near_first;
             if ((prefix || near_now) && C > 0) {  // the tiles whose walk passed their sorted prefix (usually none)
                 if (near_now)  // their far instances first (none emitted by K3); their accumulator rows zeroed
@@ -1102,7 +1108,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
     // (also with R == 0: gauss_reduce still reads every Gaussian's record start)
     if (!atomic && !mark.recs) {  // a forward that left no record inputs (or a buffer never seen)
         HIP_TRY(launch_rec_prep(P, geom, bin, C, stream), "record prep");
-        geom_mark(geom_buffer, mark.zeroed, true, mark.long_lists);
+        geom_mark(geom_buffer, mark.zeroed, true, mark.long_lists, mark.half_fwd);
     }
     if (R > 0) {
         StageScope sc(ST_RENDER_BWD, stream);
@@ -1272,6 +1278,60 @@ int gsr_render_alpha(int width, int height, const void* image_buffer, float* out
     size_t tmp = 0;
     const ImageState img = carve_image((char*)const_cast<void*>(image_buffer), width, height, gx * gy, &tmp);
     HIP_TRY(launch_render_alpha(img.final_T, out_alpha, width, height, (hipStream_t)stream), "render_alpha");
+    return GSR_OK;
+}
+
+// Every forward path (exact, capacity hint, rebuild after a short hint, redone tiles, the census kernels, any
+// fwd_quads / seg_ck / sort_prefix / near_mass / bwd_atomic setting) ends in launch_render_fwd [+ the redo], whose
+// waves write the checkpoints, the blend masks, n_contrib and the work list unconditionally: the statistics are
+// valid after all of them, and no forward state has to be refused here.
+int gsr_contrib_stats(int P, int R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                      const void* image_buffer, int binning_capacity, size_t binning_bytes, const float* pixel_weight,
+                      int accumulate, float* stats, void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0)
+        return fail(GSR_ERR_ARGUMENT, "contrib_stats: invalid sizes P=%d R=%d W=%d H=%d", P, R, width, height);
+    if (P >= kMaxGaussians)
+        return fail(GSR_ERR_ARGUMENT, "contrib_stats: P=%d exceeds the tile-list entry limit %d", P, kMaxGaussians - 1);
+    if (P == 0) return GSR_OK;
+    if (!stats) return fail(GSR_ERR_ARGUMENT, "contrib_stats: null stats");
+    if ((reinterpret_cast<uintptr_t>(stats) & 15) != 0)
+        return fail(GSR_ERR_ARGUMENT, "contrib_stats: stats must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(pixel_weight) & 3) != 0)
+        return fail(GSR_ERR_ARGUMENT, "contrib_stats: pixel_weight must be 4-byte aligned");
+    const uint32_t gx = (width + kTile - 1) / kTile, gy = (height + kTile - 1) / kTile;
+    const uint32_t tiles = gx * gy;
+    size_t C = 0;
+    if (R > 0) {
+        if (!geom_buffer || !image_buffer || !binning_buffer)
+            return fail(GSR_ERR_ARGUMENT, "contrib_stats: missing forward buffers");
+        if (!resolve_capacity(R, binning_capacity, binning_bytes, &C))
+            return fail(GSR_ERR_ARGUMENT,
+                        "contrib_stats: a binning buffer of %zu bytes matches no layout for R=%d (capacity %d)",
+                        binning_bytes, R, binning_capacity);
+        if (C < (size_t)R) return fail(GSR_ERR_ARGUMENT, "contrib_stats: binning capacity %zu < R=%d", C, R);
+    }
+    if (!accumulate) HIP_TRY(hipMemsetAsync(stats, 0, 4 * sizeof(float) * (size_t)P, stream), "contrib_stats zero");
+    if (R == 0) return GSR_OK;
+    size_t tmp = 0;
+    const GeomState geom = carve_geom((char*)const_cast<void*>(geom_buffer), P, gx, gy, &tmp);
+    const ImageState img = carve_image((char*)const_cast<void*>(image_buffer), width, height, tiles, &tmp);
+    const BinningState bin = carve_binning((char*)const_cast<void*>(binning_buffer), C, &tmp);
+    ContribArgs ca{};
+    ca.W = width; ca.H = height; ca.gx = gx; ca.gy = gy; ca.n_gauss = (uint32_t)P;
+    ca.ranges = img.ranges; ca.gid_sorted = bin.gid_sorted; ca.rec = geom.rec; ca.n_contrib = img.n_contrib;
+    // the checkpoints only where their T is known to round as the kernel's own (a half-tile forward this library
+    // ran into this geometry buffer); after a whole-tile forward, or for buffers it has not seen (copies), each unit
+    // re-walks its tile's list for T instead, and weight_max / pixel_count come out the same bits either way
+    ca.ckpt = geom_marked(geom_buffer).half_fwd ? bin.ckpt : nullptr; ca.unit_cnt = geom.unit_cnt; ca.unit_part = geom.unit_part; ca.unit_full = bin.unit_full;
+    ca.full_cap = (uint32_t)unit_full_cap(C);
+    ca.seg_ck = geom.fwd_seg_ck;
+    ca.pixel_weight = pixel_weight;
+    ca.stats = stats;
+    // (sized like the backward's grid: for the shortest segments, whatever the forward used)
+    HIP_TRY(launch_contrib_stats(ca, bwd_max_units((size_t)R, tiles, 1), stream, option(OPT_BWD_GRID)), "contrib_stats");
     return GSR_OK;
 }
 

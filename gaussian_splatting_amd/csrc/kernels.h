@@ -120,6 +120,27 @@ struct RenderBwdArgs {
     int absgrad;
 };
 
+// Per-Gaussian contribution statistics (contrib.hip, include/gsr.h gsr_contrib_stats): a read-only walk of a
+// finished forward's tile lists over the backward's work list.
+struct ContribArgs {
+    int W, H;
+    uint32_t gx, gy;
+    uint32_t n_gauss;
+    const uint2* ranges;
+    const uint32_t* gid_sorted;   // with the forward's blend masks
+    const float4* rec;
+    const uint32_t* n_contrib;    // ImageState::n_contrib (tile-major)
+    const float* ckpt;            // blend checkpoints (only the T plane is read), or null: each unit re-walks its
+                                  // tile's list from the head for T (contrib.hip CKPT)
+    const uint32_t* unit_cnt;
+    const uint2* unit_part;
+    const uint2* unit_full;
+    uint32_t full_cap;
+    const uint32_t* seg_ck;       // GeomState::fwd_seg_ck
+    const float* pixel_weight;    // [H,W] row-major, or null (non-null selects the WEIGHTED instantiations)
+    float* stats;                 // [P][4]: weight_sum, weight_max, pixel_count (u32 bits), weighted_sum
+};
+
 struct GaussBwdArgs {
     int P, D, M, W, H;
     const float* means3D;
@@ -450,6 +471,9 @@ hipError_t launch_render_bwd(const RenderBwdArgs& a, size_t max_units, hipStream
 // backward work list: one unit per (tile, segment of seg_ck * kCkStride entries below the tile's limit),
 // written by the forward render; at most R / (seg_ck kCkStride) + tiles of them
 size_t bwd_max_units(size_t R, uint32_t tiles, int seg_ck);
+// contrib.hip: one wave per unit of the backward's work list, the grid sized as launch_render_bwd's (max_units
+// and grid_mode as there); adds / maxes into ContribArgs::stats, which the caller has zeroed or wants combined
+hipError_t launch_contrib_stats(const ContribArgs& a, size_t max_units, hipStream_t stream, int grid_mode = 0);
 // Longest reachable prefix K4 sorts ("sort_prefix" option range; binning.hip kPrefixBuf holds twice it).
 constexpr uint32_t kSortPrefixMax = 1024;
 // backward.hip

@@ -42,7 +42,7 @@ from torch import nn
 from . import _lib
 
 __all__ = ["add_densification_stats", "update_max_radii", "densification_stats", "densify_and_prune", "install",
-           "GROUPS"]
+           "prune_mask_by_contribution", "GROUPS"]
 
 COPY, XYZ, SCALING = 0, 1, 2  # GSR_DENSIFY_COPY / _XYZ / _SCALING
 # optimizer group name, model attribute, how children rows are made
@@ -250,6 +250,30 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, rad
     model.denom = torch.zeros((P_new, 1), device=device)
     model.max_radii2D = torch.zeros((P_new), device=device)
     model.tmp_radii = None
+
+
+def prune_mask_by_contribution(score: torch.Tensor, keep_ratio: float = None, threshold: float = None) -> torch.Tensor:
+    """The bool mask [P] the reference's own ``GaussianModel.prune_points(mask)`` takes (True = remove;
+    gaussian_model.py:420-437, pure torch, runs unchanged) from a per-Gaussian importance ``score`` [P] -- e.g. a
+    column of the contribution statistics (``gaussian_splatting_amd.contrib``) accumulated over the training views.
+
+    ``keep_ratio`` in [0, 1]: exactly ``ceil(keep_ratio * P)`` Gaussians are kept, those of highest score, equal
+    scores in index order (the lower index is kept).  ``threshold``: Gaussians with ``score < threshold`` are
+    removed.  With both, a Gaussian is kept only if both keep it.  Plain tensor arithmetic on ``score``'s device."""
+    if keep_ratio is None and threshold is None:
+        raise ValueError("prune_mask_by_contribution: give keep_ratio, threshold or both")
+    score = score.detach().reshape(-1)
+    P = score.numel()
+    prune = torch.zeros(P, dtype=torch.bool, device=score.device)
+    if keep_ratio is not None:
+        if not 0.0 <= float(keep_ratio) <= 1.0:
+            raise ValueError(f"prune_mask_by_contribution: keep_ratio {keep_ratio} outside [0, 1]")
+        k = min(P, int(math.ceil(float(keep_ratio) * P)))
+        order = torch.argsort(score, descending=True, stable=True)  # (stable: ties stay in index order)
+        prune[order[k:]] = True
+    if threshold is not None:
+        prune |= score < threshold
+    return prune
 
 
 def install(cls) -> None:

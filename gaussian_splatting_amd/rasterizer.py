@@ -40,7 +40,7 @@ class GaussianRasterizationSettings(NamedTuple):
     antialiasing: bool
 
 
-def rasterize_gaussians(*args, return_alpha=False, absgrad=False):
+def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib=False, contrib_weight=None):
     """``rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
     raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``.
 
@@ -50,11 +50,20 @@ def rasterize_gaussians(*args, return_alpha=False, absgrad=False):
     ``absgrad=True`` (an extension, gsplat's convention): the backward of this render also sets
     ``means2D.absgrad`` [P,3] (float32, on the device): per Gaussian the sum over pixels of the ABSOLUTE value of
     each pixel's term of ``means2D.grad`` (AbsGS; include/gsr.h gsr_rasterize_backward_abs), column 2 zero.  Each
-    backward overwrites it.  Without the keyword no attribute is set and nothing more is launched or allocated."""
+    backward overwrites it.  Without the keyword no attribute is set and nothing more is launched or allocated.
+
+    ``return_contrib=True`` (an extension): one more output, LAST (after ``alpha`` when both are asked for): the
+    per-Gaussian contribution statistics [P,4] of this render (include/gsr.h gsr_contrib_stats; named views:
+    ``gaussian_splatting_amd.contrib.split``), computed in the node's forward from the buffers it saves anyway and
+    not differentiable.  ``contrib_weight`` ([H,W] or [1,H,W], only with ``return_contrib``) is the per-pixel map of
+    the ``weighted_sum`` column.  Without the keywords nothing more is launched or allocated."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
     _RasterizeGaussians._return_alpha.value = bool(return_alpha)  # (read and cleared by the node's forward)
     _RasterizeGaussians._absgrad.value = bool(absgrad)            # (likewise)
+    if contrib_weight is not None and not return_contrib:
+        raise TypeError("rasterize_gaussians(): contrib_weight needs return_contrib=True")
+    _RasterizeGaussians._contrib.value = (contrib_weight,) if return_contrib else None  # (likewise)
     # Camera-pose gradients: when a camera tensor of the settings requires grad (and grad mode is on) the three
     # enter the autograd node as explicit inputs after the settings; every other render takes the path below.
     s = args[-1]
@@ -83,6 +92,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     _no_backward = threading.local()
     _return_alpha = threading.local()  # set by rasterize_gaussians(..., return_alpha=True) for its one call
     _absgrad = threading.local()       # set by rasterize_gaussians(..., absgrad=True) for its one call
+    _contrib = threading.local()       # set by rasterize_gaussians(..., return_contrib=True): (contrib_weight,)
 
     @staticmethod
     def _absgrad_kw(ctx):
@@ -133,6 +143,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         # absgrad: the node keeps means2D (its value is never read) and its backward sets means2D.absgrad
         ctx.absgrad_of = means2D if getattr(_RasterizeGaussians._absgrad, "value", False) else None
         _RasterizeGaussians._absgrad.value = False
+        contrib = getattr(_RasterizeGaussians._contrib, "value", None)
+        _RasterizeGaussians._contrib.value = None
         if with_alpha:
             num_rendered, color, radii, geom, binning, img, invdepths, alpha = _C.rasterize_gaussians(
                 *head, *sh_args, *tail, no_backward=no_backward, return_alpha=True)
@@ -145,8 +157,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.separate_sh = dc is not None
         saved = (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning, img)
         ctx.save_for_backward(*saved, *(() if dc is None else (dc,)))
-        ctx.mark_non_differentiable(radii)
-        return (color, radii, invdepths, alpha) if with_alpha else (color, radii, invdepths)
+        outs = (color, radii, invdepths, alpha) if with_alpha else (color, radii, invdepths)
+        if contrib is None:
+            ctx.mark_non_differentiable(radii)
+            return outs
+        # the statistics of this forward, from the buffers saved above (read-only: the backward is unaffected)
+        stats = _C.contribution_stats(geom, binning, img, num_rendered, means3D.size(0), s.image_height, s.image_width,
+                                      pixel_weight=contrib[0])
+        ctx.mark_non_differentiable(radii, stats)
+        return outs + (stats,)
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, *grad_alpha):
@@ -240,12 +259,15 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None, return_alpha=False, absgrad=False):
+                cov3D_precomp=None, dc=None, return_alpha=False, absgrad=False, return_contrib=False,
+                contrib_weight=None):
         """Same checks as the reference (:242-261).  ``dc=`` (keyword) selects the 3DGS-accel separate-SH
         input: ``dc`` = ``_features_dc`` [P,1,3] and ``shs`` = ``_features_rest`` [P,M,3]
         (gaussian_renderer/__init__.py:115-125).  ``return_alpha=True`` returns ``(color, radii, invdepths,
         alpha)`` with the differentiable accumulated-alpha map [1,H,W] (``rasterize_gaussians``).
-        ``absgrad=True``: the backward also sets ``means2D.absgrad`` (``rasterize_gaussians``)."""
+        ``absgrad=True``: the backward also sets ``means2D.absgrad`` (``rasterize_gaussians``).
+        ``return_contrib=True`` [+ ``contrib_weight=``]: the per-Gaussian contribution statistics [P,4] as the last
+        output (``rasterize_gaussians``)."""
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -258,9 +280,12 @@ class GaussianRasterizer(nn.Module):
         scales = empty if scales is None else scales
         rotations = empty if rotations is None else rotations
         cov3D_precomp = empty if cov3D_precomp is None else cov3D_precomp
+        # (no keyword at all without the request: the call is then the one without the feature)
+        contrib_kw = dict(return_contrib=True, contrib_weight=contrib_weight) if return_contrib else (
+            {} if contrib_weight is None else dict(contrib_weight=contrib_weight))
         if dc is None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad)
+                                       cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad, **contrib_kw)
         dc = empty if colors_precomp.numel() != 0 else dc
         return rasterize_gaussians(means3D, means2D, dc, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad)
+                                   cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad, **contrib_kw)

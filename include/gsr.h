@@ -225,6 +225,37 @@ int gsr_rasterize_backward_abs(int P, int D, int M, int R, const float* backgrou
                                gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream, int binning_capacity,
                                size_t binning_bytes, float* dL_dmean2D_abs);
 
+/* Per-Gaussian contribution statistics (importance pruning: LightGaussian's global significance, RadSplat's
+ * max-blend-weight pruning, visibility-count prunes).  The blend weight of Gaussian g at pixel pix is
+ * w(g, pix) = alpha(g, pix) T(g, pix), the factor of g's colour in out_color (CR/forward.cu:484-489).  A
+ * (Gaussian, pixel) pair contributes iff the forward blended it: alpha >= 1/255, power <= 0, and the pair lies
+ * before the pixel's termination -- the pairs the backward forms a gradient term for.  The maximum and the count
+ * cannot be had from any backward (autograd only sees sums), so they are formed by a pass of their own.
+ *
+ * gsr_contrib_stats: from the three buffers of a finished forward (any of the three forwards, under every option,
+ *   also one no backward will follow; P, R, width, height, binning_capacity / binning_bytes as
+ *   gsr_rasterize_backward_ex takes them) into stats ([P,4], device, 16-byte aligned), row g =
+ *     weight_sum    f32       sum of w over g's contributing pixels
+ *     weight_max    f32       max of w over them
+ *     pixel_count   u32 bits  their number
+ *     weighted_sum  f32       sum of w m(pix), m = pixel_weight ([H,W] row-major); 0 when pixel_weight is NULL
+ *   accumulate == 0: every row is written; rows of culled or never-blended Gaussians are zero, and P == 0 or
+ *   R == 0 gives zeros (P == 0 launches nothing and the buffers may be NULL; R == 0 needs only stats).
+ *   accumulate != 0: rows are combined with what they hold -- sums and counts add, the maximum maxes -- so one
+ *   buffer accumulates any number of views with no extra pass; the caller zeroes it first.  Counts wrap at 2^32.
+ *   weight_max and pixel_count do not depend on summation order and are bitwise reproducible; the two sums add
+ *   each tile instance's share with float atomics, in the hardware's order.  The call reads the forward's
+ *   buffers and writes only stats: a backward of the same forward, before or after it, is unaffected, and it may
+ *   be repeated.  It runs on `stream`, which must be the forward's or ordered behind it.  Not differentiable.  The
+ *   census (gsr_census_set) does not apply and the stage profiler does not time the call.  Multi-GPU: each rank
+ *   computes its views' rows; all-reduce the four columns with SUM, MAX, SUM, SUM.
+ *   GSR_ERR_ARGUMENT on negative or zero sizes, a NULL or misaligned stats, missing buffers with R > 0, or a
+ *   binning buffer whose size matches no layout for R. */
+int gsr_contrib_stats(int P, int R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                      const void* image_buffer, int binning_capacity, size_t binning_bytes,
+                      const float* pixel_weight /* [H,W] row-major or NULL */, int accumulate,
+                      float* stats /* [P,4], 16-byte aligned */, void* stream);
+
 /* Multi-GPU view exchange (gaussian_splatting_amd/distributed.py
  * ViewExchange).  The reference trains on one GPU; sharding views over N ranks needs the
  * N views' parameter gradients summed on every rank.  Instead of all-reducing the 59-float
