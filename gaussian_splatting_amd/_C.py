@@ -25,7 +25,8 @@ __all__ = ["rasterize_gaussians", "rasterize_gaussians_backward", "rasterize_gau
            "gauss_backward_views", "view_block_floats", "view_pack_floats", "view_block_pack", "view_block_unpack", "view_block_index",
            "views_live_floats", "views_live_list",
            "mark_visible", "adamUpdate", "fusedssim",
-           "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha", "contribution_stats"]
+           "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha", "contribution_stats",
+           "render_features", "render_features_backward", "feature_chunk", "check_features"]
 
 
 # Sync-free forward (gsr_rasterize_forward_ex): the binning buffer is sized from a capacity
@@ -214,6 +215,101 @@ def contribution_stats(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, im
             _stream_handle(device))
     _lib.check(rc, "contribution_stats")
     return stats
+
+
+def feature_chunk() -> int:
+    """Channels one wave of the feature kernels blends at once (include/gsr.h gsr_render_features_chunk): a feature
+    render of C channels runs ceil(C / feature_chunk()) waves per tile."""
+    return int(_lib.load().gsr_render_features_chunk())
+
+
+def check_features(features, P: int, device=None) -> None:
+    """The argument check of every ``features=`` entry: a contiguous float32 HIP-device [P,C] tensor, C >= 1 (on
+    ``device`` when given)."""
+    if not isinstance(features, torch.Tensor):
+        raise TypeError(f"features: expected a tensor, got {type(features).__name__}")
+    if features.dim() != 2 or features.size(0) != int(P) or features.size(1) < 1:
+        raise RuntimeError(f"features must have dimensions (num_points, C) with C >= 1, i.e. ({int(P)}, C); got "
+                           f"{tuple(features.shape)}")
+    if features.dtype != torch.float32:
+        raise RuntimeError(f"features: expected a float32 tensor, got {features.dtype}")
+    _require_device(features, "features")
+    if device is not None and features.device != device:
+        raise RuntimeError(f"features: tensor on {features.device}, expected {device}")
+    if not features.is_contiguous():
+        raise RuntimeError("features: expected a contiguous [P,C] tensor (call .contiguous())")
+
+
+def _feature_buffers(geomBuffer, binningBuffer, imgBuffer):
+    return (geomBuffer.data_ptr() if geomBuffer.numel() else None,
+            binningBuffer.data_ptr() if binningBuffer.numel() else None,
+            imgBuffer.data_ptr() if imgBuffer.numel() else None, 0, int(binningBuffer.numel()))
+
+
+def render_features(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imgBuffer: torch.Tensor,
+                    num_rendered: int, P: int, image_height: int, image_width: int,
+                    features: torch.Tensor) -> torch.Tensor:
+    """The feature map [C,H,W] of ``features`` [P,C] blended with the weights of the forward that filled the three
+    buffers (include/gsr.h gsr_render_features), on the current stream: ``sum_g alpha_g T_g features[g]`` per pixel,
+    no background.  Read-only on the buffers (copies are accepted, a backward may precede or follow), bitwise
+    reproducible; zeros when there are no Gaussians or none was rendered."""
+    P, H, W = int(P), int(image_height), int(image_width)
+    check_features(features, P)
+    device = features.device
+    C = int(features.size(1))
+    f32 = dict(dtype=torch.float32, device=device)
+    if P == 0:
+        return torch.zeros((C, H, W), **f32)
+    out = _empty((C, H, W), **f32)  # every element is written
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_features(P, C, int(num_rendered), W, H,
+                                             *_feature_buffers(geomBuffer, binningBuffer, imgBuffer),
+                                             features.data_ptr(), out.data_ptr(), _stream_handle(device))
+    _lib.check(rc, "render_features")
+    return out
+
+
+def render_features_backward(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imgBuffer: torch.Tensor,
+                             num_rendered: int, P: int, image_height: int, image_width: int, features: torch.Tensor,
+                             feature_map: torch.Tensor, dL_dfeature_map: torch.Tensor, geometry=None) -> tuple:
+    """The backward of ``render_features`` (include/gsr.h gsr_render_features_backward): returns ``(dL_dfeatures
+    [P,C], view_block)``.  ``geometry`` None (frozen geometry): only ``dL_dfeatures``, ``view_block`` is None.
+    Otherwise a dict with ``viewmatrix, projmatrix, campos, tanfovx, tanfovy, antialiasing, radii``: the feature
+    loss's per-Gaussian screen-space sums are also written, as a view block of ``view_block_floats(P)`` floats
+    for ``gauss_backward_views`` (one view; ``dL_dmeans2D`` is
+    ``view_block[64 + 4 * P:64 + 8 * P].view(P, 4)[:, :2]``)."""
+    P, H, W = int(P), int(image_height), int(image_width)
+    check_features(features, P)
+    device = features.device
+    C = int(features.size(1))
+    f32 = dict(dtype=torch.float32, device=device)
+    for name, t in (("feature_map", feature_map), ("dL_dfeature_map", dL_dfeature_map)):
+        if tuple(t.shape) != (C, H, W) or t.dtype != torch.float32 or t.device != device:
+            raise RuntimeError(f"{name}: expected a float32 {(C, H, W)} tensor on {device}, got {t.dtype} "
+                               f"{tuple(t.shape)} on {t.device}")
+    if P == 0:
+        return torch.zeros((0, C), **f32), (None if geometry is None else torch.zeros(view_block_floats(0), **f32))
+    ins = _Inputs(device)
+    dL_dF = _empty((P, C), **f32)  # every element is written
+    block = None
+    cam = (None, None, None, 0.0, 0.0, 0, None)
+    scratch = torch.empty(0, dtype=torch.uint8, device=device)
+    rs = _Resizer(scratch)
+    if geometry is not None:
+        g = geometry
+        block = _empty((view_block_floats(P),), **f32)
+        campos = g["campos"] if g["campos"].device.type == "cuda" else g["campos"].to(device)
+        cam = (ins.req(g["viewmatrix"], "viewmatrix", small=True), ins.req(g["projmatrix"], "projmatrix", small=True),
+               ins.req(campos, "campos"), float(g["tanfovx"]), float(g["tanfovy"]), int(bool(g["antialiasing"])),
+               ins.radii(g["radii"]))
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_features_backward(
+            P, C, int(num_rendered), W, H, *_feature_buffers(geomBuffer, binningBuffer, imgBuffer),
+            features.data_ptr(), ins.req(feature_map, "feature_map"), ins.req(dL_dfeature_map, "dL_dfeature_map"),
+            dL_dF.data_ptr(), block.data_ptr() if block is not None else None, *cam, rs.cb, None,
+            _stream_handle(device))
+    _lib.check(rc, "render_features_backward")
+    return dL_dF, block
 
 
 def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = False) -> tuple:

@@ -1335,6 +1335,142 @@ int gsr_contrib_stats(int P, int R, int width, int height, const void* geom_buff
     return GSR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The arguments the two feature calls share, checked, and the walk's view of the three buffers.  Returns GSR_OK with
+// *walk false when there is nothing to walk (P == 0 or R == 0).
+int features_args(const char* who, int P, int C, int R, int width, int height, const void* geom_buffer,
+                  const void* binning_buffer, const void* image_buffer, int binning_capacity, size_t binning_bytes,
+                  gsr::FeatureArgs* fa, bool* walk) {
+    using namespace gsr;
+    *walk = false;
+    if (P < 0 || R < 0 || width <= 0 || height <= 0)
+        return fail(GSR_ERR_ARGUMENT, "%s: invalid sizes P=%d R=%d W=%d H=%d", who, P, R, width, height);
+    if (C <= 0 || (C + kFeatChunk - 1) / kFeatChunk > 65535)
+        return fail(GSR_ERR_ARGUMENT, "%s: C=%d channels (1 .. %d)", who, C, 65535 * kFeatChunk);
+    if (P >= kMaxGaussians)
+        return fail(GSR_ERR_ARGUMENT, "%s: P=%d exceeds the tile-list entry limit %d", who, P, kMaxGaussians - 1);
+    const uint32_t gx = (width + kTile - 1) / kTile, gy = (height + kTile - 1) / kTile;
+    fa->W = width; fa->H = height; fa->C = C; fa->gx = gx; fa->gy = gy; fa->n_gauss = (uint32_t)P;
+    if (P == 0 || R == 0) return GSR_OK;
+    if (!geom_buffer || !image_buffer || !binning_buffer)
+        return fail(GSR_ERR_ARGUMENT, "%s: missing forward buffers", who);
+    size_t cap = 0;
+    if (!resolve_capacity(R, binning_capacity, binning_bytes, &cap))
+        return fail(GSR_ERR_ARGUMENT, "%s: a binning buffer of %zu bytes matches no layout for R=%d (capacity %d)", who,
+                    binning_bytes, R, binning_capacity);
+    if (cap < (size_t)R) return fail(GSR_ERR_ARGUMENT, "%s: binning capacity %zu < R=%d", who, cap, R);
+    size_t tmp = 0;
+    const GeomState geom = carve_geom((char*)const_cast<void*>(geom_buffer), P, gx, gy, &tmp);
+    const ImageState img = carve_image((char*)const_cast<void*>(image_buffer), width, height, gx * gy, &tmp);
+    const BinningState bin = carve_binning((char*)const_cast<void*>(binning_buffer), cap, &tmp);
+    fa->n_entries = (uint32_t)std::min(cap, (size_t)UINT32_MAX);
+    fa->ranges = img.ranges; fa->gid_sorted = bin.gid_sorted; fa->rec = geom.rec; fa->n_contrib = img.n_contrib;
+    *walk = true;
+    return GSR_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// Like gsr_contrib_stats the two feature calls need only what every forward path leaves behind (the sorted lists
+// with the blend masks, the records, n_contrib), and they walk whole lists from the head: no checkpoint, no work
+// list, no forward state is consulted, so no forward has to be refused.
+int gsr_render_features(int P, int C, int R, int width, int height, const void* geom_buffer,
+                        const void* binning_buffer, const void* image_buffer, int binning_capacity,
+                        size_t binning_bytes, const float* features, float* out_features, void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    FeatureArgs fa{};
+    bool walk = false;
+    if (int rc = features_args("render_features", P, C, R, width, height, geom_buffer, binning_buffer, image_buffer,
+                               binning_capacity, binning_bytes, &fa, &walk))
+        return rc;
+    if (!out_features || (P > 0 && !features)) return fail(GSR_ERR_ARGUMENT, "render_features: null pointer");
+    if (!walk) {
+        HIP_TRY(hipMemsetAsync(out_features, 0, sizeof(float) * (size_t)C * width * height, stream),
+                "render_features zero");
+        return GSR_OK;
+    }
+    fa.features = features;
+    fa.out = out_features;
+    HIP_TRY(launch_features_fwd(fa, stream), "render_features");
+    return GSR_OK;
+}
+
+int gsr_render_features_backward(int P, int C, int R, int width, int height, const void* geom_buffer,
+                                 const void* binning_buffer, const void* image_buffer, int binning_capacity,
+                                 size_t binning_bytes, const float* features, const float* out_features,
+                                 const float* dL_dout_features, float* dL_dfeatures, float* view_block,
+                                 const float* viewmatrix, const float* projmatrix, const float* campos,
+                                 float tan_fovx, float tan_fovy, int antialiasing, const int* radii,
+                                 gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    FeatureArgs fa{};
+    bool walk = false;
+    if (int rc = features_args("render_features_backward", P, C, R, width, height, geom_buffer, binning_buffer,
+                               image_buffer, binning_capacity, binning_bytes, &fa, &walk))
+        return rc;
+    if (P == 0) return GSR_OK;
+    if (!features || !dL_dout_features || !dL_dfeatures || (view_block && !out_features))
+        return fail(GSR_ERR_ARGUMENT, "render_features_backward: null pointer");
+    if (view_block) {
+        if ((reinterpret_cast<uintptr_t>(view_block) & 15) != 0)
+            return fail(GSR_ERR_ARGUMENT, "render_features_backward: view block must be 16-byte aligned");
+        if (!viewmatrix || !projmatrix || !campos || !radii || !geom_buffer)
+            return fail(GSR_ERR_ARGUMENT, "render_features_backward: the view block needs the camera, radii and the "
+                                          "geometry buffer");
+    }
+    HIP_TRY(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)P * C, stream), "render_features_backward zero");
+    float4* acc = nullptr;
+    uint32_t* touched = nullptr;
+    if (view_block) {  // scratch accumulator rows and touched bits, zeroed (gauss_live_views leaves them zero again)
+        Carver c{nullptr, 0};
+        c.take<float4>((size_t)kAccRow4 * P);
+        c.take<uint32_t>(touched_words((size_t)P));
+        const size_t bytes = align_up(c.off);
+        char* base = (char*)call_alloc(scratch_alloc, scratch_ctx, bytes);
+        if (!base) return fail(GSR_ERR_ALLOC, "render_features_backward: scratch allocation failed");
+        Carver d{base, 0};
+        acc = d.take<float4>((size_t)kAccRow4 * P);
+        touched = d.take<uint32_t>(touched_words((size_t)P));
+        HIP_TRY(hipMemsetAsync(base, 0, bytes, stream), "render_features_backward scratch zero");
+    }
+    if (walk) {
+        fa.features = features;
+        fa.fmap = out_features;
+        fa.dL_dfmap = dL_dout_features;
+        fa.dL_dfeatures = dL_dfeatures;
+        fa.acc = reinterpret_cast<float*>(acc);
+        fa.touched = touched;
+        HIP_TRY(launch_features_bwd(fa, stream), "render_features_backward");
+    }
+    if (view_block) {
+        // the view block of this loss alone: colour and inverse-depth sums zero, the flags from radii and the
+        // forward's SH clamp bits, the camera header (no inverse-depth term)
+        float* body = view_block + kViewBlockHeader;
+        GradRecs sums{};
+        sums.a = reinterpret_cast<float4*>(body);
+        sums.b = reinterpret_cast<float4*>(body + 4 * (size_t)P);
+        sums.c = reinterpret_cast<float2*>(body + 8 * (size_t)P);
+        uint32_t* flags = reinterpret_cast<uint32_t*>(body + 10 * (size_t)P);
+        HIP_TRY(launch_gauss_live_views(P, touched, acc, radii, geom_clamped(geom_buffer, P, width, height), sums, flags,
+                                        stream),
+                "render_features_backward view block");
+        const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
+        HIP_TRY(launch_view_header(view_block, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, focal_x, focal_y,
+                                   antialiasing, 0, stream),
+                "render_features_backward view header");
+    }
+    return GSR_OK;
+}
+
+int gsr_render_features_chunk(void) { return gsr::kFeatChunk; }
+
 int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
                                  const float* means3D, const float* dc, const float* shs,
                                  const float* colors_precomp, const float* opacities, const float* scales,

@@ -141,6 +141,28 @@ struct ContribArgs {
     float* stats;                 // [P][4]: weight_sum, weight_max, pixel_count (u32 bits), weighted_sum
 };
 
+// N-channel feature rendering (features.hip, include/gsr.h gsr_render_features / gsr_render_features_backward):
+// read-only walks of a finished forward's whole tile lists, one wave per (tile, chunk of kFeatChunk channels).
+constexpr int kFeatChunk = 16;    // channels a wave blends at once (its accumulators: 4 quadrants x kFeatChunk registers)
+struct FeatureArgs {
+    int W, H, C;                  // C: channels (any >= 1)
+    uint32_t gx, gy;
+    uint32_t n_gauss;
+    uint32_t n_entries;           // the binning capacity: a tile range reaching past it is not walked
+    const uint2* ranges;
+    const uint32_t* gid_sorted;   // with the forward's blend masks
+    const float4* rec;
+    const uint32_t* n_contrib;    // ImageState::n_contrib (tile-major)
+    const float* features;        // [P,C]
+    float* out;                   // forward: Fmap [C,H,W], every element written
+    // backward
+    const float* fmap;            // [C,H,W] the forward's map (read with acc only)
+    const float* dL_dfmap;        // [C,H,W]
+    float* dL_dfeatures;          // [P,C], zeroed by the caller, added into
+    float* acc;                   // [P][4 * kAccRow4] scratch accumulator rows (GeomState::acc's layout), zeroed by the
+    uint32_t* touched;            // caller, and their touched bits; both null: no geometry part
+};
+
 struct GaussBwdArgs {
     int P, D, M, W, H;
     const float* means3D;
@@ -474,6 +496,9 @@ size_t bwd_max_units(size_t R, uint32_t tiles, int seg_ck);
 // contrib.hip: one wave per unit of the backward's work list, the grid sized as launch_render_bwd's (max_units
 // and grid_mode as there); adds / maxes into ContribArgs::stats, which the caller has zeroed or wants combined
 hipError_t launch_contrib_stats(const ContribArgs& a, size_t max_units, hipStream_t stream, int grid_mode = 0);
+// features.hip: one wave per (tile, channel chunk); the backward's geometry variant is picked by FeatureArgs::acc
+hipError_t launch_features_fwd(const FeatureArgs& a, hipStream_t stream);
+hipError_t launch_features_bwd(const FeatureArgs& a, hipStream_t stream);
 // Longest reachable prefix K4 sorts ("sort_prefix" option range; binning.hip kPrefixBuf holds twice it).
 constexpr uint32_t kSortPrefixMax = 1024;
 // backward.hip

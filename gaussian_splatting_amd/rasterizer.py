@@ -14,7 +14,7 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansCamera", "cpu_deep_copy_tuple"]
+           "_RasterizeGaussiansCamera", "_RenderFeatures", "cpu_deep_copy_tuple"]
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -40,7 +40,94 @@ class GaussianRasterizationSettings(NamedTuple):
     antialiasing: bool
 
 
-def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib=False, contrib_weight=None):
+def _rasterize_with_features(args, features, kw):
+    """``rasterize_gaussians(..., features=F)``: the render without the keyword, whose node hands its buffers over, then
+    the feature node behind it; ``feature_map`` goes after ``alpha`` and before the contribution statistics."""
+    means3D, means2D = args[0], args[1]
+    s = args[-1]
+    scales, rotations, cov3D = args[-4], args[-3], args[-2]
+    opacities = args[-5]
+    if not isinstance(means3D, torch.Tensor) or means3D.dim() != 2:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    has_cov = isinstance(cov3D, torch.Tensor) and cov3D.numel() != 0
+    geom_in = (means3D, means2D, opacities, scales, rotations)
+    if has_cov and torch.is_grad_enabled() and any(
+            isinstance(t, torch.Tensor) and t.requires_grad for t in geom_in + (cov3D,)):
+        raise RuntimeError("features= with cov3D_precomp cannot give a geometry gradient of the feature loss (its "
+                           "per-Gaussian backward needs scales and rotations): detach the geometry inputs for this "
+                           "render, or pass scales and rotations")
+    _C.check_features(features, means3D.size(0), means3D.device if means3D.device.type == "cuda" else None)
+    _RasterizeGaussians._features.value = True  # (read by the node's forward, which leaves its buffers there)
+    try:
+        outs = rasterize_gaussians(*args, **kw)
+        handed = getattr(_RasterizeGaussians._features, "value", None)
+    finally:
+        _RasterizeGaussians._features.value = None
+    if not isinstance(handed, tuple):
+        raise RuntimeError("rasterize_gaussians(features=): the render did not hand over its buffers")
+    geom, binning, img, num_rendered = handed
+    empty = means3D.new_empty(0)
+    fmap = _RenderFeatures.apply(features, means3D, means2D, opacities,
+                                 empty if has_cov else scales, empty if has_cov else rotations,
+                                 outs[1], geom, binning, img, s, num_rendered)
+    n = 4 if kw.get("return_alpha") else 3
+    return outs[:n] + (fmap,) + outs[n:]
+
+
+class _RenderFeatures(torch.autograd.Function):
+    """The feature node behind the rasterizer node: forward = ``_C.render_features`` over the rasterizer node's buffers
+    (non-differentiable inputs), backward = ``_C.render_features_backward`` and, when a geometry input needs a
+    gradient, ``_C.gauss_backward_views`` over the one view block it fills.  Inputs ``(features, means3D, means2D,
+    opacities, scales, rotations, radii, geom, binning, img, raster_settings, num_rendered)``; ``means2D`` only
+    receives the feature loss's screen-space gradient, which autograd adds to the colour's."""
+
+    @staticmethod
+    def forward(ctx, features, means3D, means2D, opacities, scales, rotations, radii, geom, binning, img, s,
+                num_rendered):
+        fmap = _C.render_features(geom, binning, img, num_rendered, means3D.size(0), s.image_height, s.image_width,
+                                  features)
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(features, fmap, means3D, opacities, scales, rotations, radii, geom, binning, img)
+        return fmap
+
+    @staticmethod
+    def backward(ctx, grad_fmap):
+        s = ctx.raster_settings
+        features, fmap, means3D, opacities, scales, rotations, radii, geom, binning, img = ctx.saved_tensors
+        P = means3D.size(0)
+        need_geom = any(ctx.needs_input_grad[1:6])
+        if need_geom and P > 0 and (scales.numel() == 0 or rotations.numel() == 0):
+            raise RuntimeError("features=: a geometry gradient of the feature loss needs scales and rotations")
+        geometry = None
+        if need_geom:
+            geometry = dict(viewmatrix=s.viewmatrix.detach(), projmatrix=s.projmatrix.detach(),
+                            campos=s.campos.detach(), tanfovx=s.tanfovx, tanfovy=s.tanfovy,
+                            antialiasing=s.antialiasing, radii=radii)
+        dL_dF, block = _C.render_features_backward(geom, binning, img, ctx.num_rendered, P, s.image_height,
+                                                   s.image_width, features, fmap, grad_fmap.contiguous(),
+                                                   geometry=geometry)
+        grad_F = dL_dF if ctx.needs_input_grad[0] else None
+        if not need_geom:
+            return (grad_F,) + (None,) * 11
+        f32 = dict(dtype=torch.float32, device=means3D.device)
+        out = {"dL_dmeans3D": torch.empty((P, 3), **f32), "dL_ddc": torch.empty((P, 1, 3), **f32),
+               "dL_dsh": torch.empty((P, 0, 3), **f32), "dL_dopacity": torch.empty((P, 1), **f32),
+               "dL_dscales": torch.empty((P, 3), **f32), "dL_drotations": torch.empty((P, 4), **f32)}
+        grad_means2D = torch.zeros((P, 3), **f32)
+        if P > 0:
+            # the view block carries no colour gradient: a zero dc of one coefficient satisfies the SH reads
+            _C.gauss_backward_views(means3D, torch.zeros((P, 1, 3), **f32), None, 0, opacities, scales, rotations,
+                                    s.scale_modifier, block.view(1, -1), out)
+            grad_means2D[:, :2] = block[64 + 4 * P:64 + 8 * P].view(P, 4)[:, :2]
+        need = ctx.needs_input_grad
+        return (grad_F, out["dL_dmeans3D"] if need[1] else None, grad_means2D if need[2] else None,
+                out["dL_dopacity"].view(opacities.shape) if need[3] else None,
+                out["dL_dscales"] if need[4] else None, out["dL_drotations"] if need[5] else None) + (None,) * 6
+
+
+def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib=False, contrib_weight=None,
+                        features=None):
     """``rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
     raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``.
 
@@ -56,9 +143,23 @@ def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib
     per-Gaussian contribution statistics [P,4] of this render (include/gsr.h gsr_contrib_stats; named views:
     ``gaussian_splatting_amd.contrib.split``), computed in the node's forward from the buffers it saves anyway and
     not differentiable.  ``contrib_weight`` ([H,W] or [1,H,W], only with ``return_contrib``) is the per-pixel map of
-    the ``weighted_sum`` column.  Without the keywords nothing more is launched or allocated."""
+    the ``weighted_sum`` column.  Without the keywords nothing more is launched or allocated.
+
+    ``features=F`` (an extension, gsplat's N-D features): ``F`` a contiguous float32 [P,C] device tensor, any C >= 1.
+    One more output ``feature_map`` [C,H,W], after ``alpha`` when that is present and before the contribution
+    statistics: ``sum_g alpha_g T_g F[g]`` per pixel with this render's own blend weights, no background term
+    (include/gsr.h gsr_render_features; one more pass over the buffers the node saves anyway instead of ceil(C/3)
+    renders).  Differentiable with respect to ``F`` and, through an autograd node of its own behind the rasterizer
+    node (``_RenderFeatures``), to ``means3D``, ``opacities``, ``scales``, ``rotations`` and ``means2D`` (so
+    ``means2D.grad`` carries the feature loss too); when only ``F`` requires grad the backward does the ``F`` work
+    alone.  The feature loss does not reach the camera tensors or ``means2D.absgrad``; with ``cov3D_precomp`` a
+    geometry input that requires grad is refused.  Without the keyword nothing more is launched or allocated."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
+    if features is not None:
+        return _rasterize_with_features(args, features, dict(return_alpha=return_alpha, absgrad=absgrad,
+                                                             return_contrib=return_contrib,
+                                                             contrib_weight=contrib_weight))
     _RasterizeGaussians._return_alpha.value = bool(return_alpha)  # (read and cleared by the node's forward)
     _RasterizeGaussians._absgrad.value = bool(absgrad)            # (likewise)
     if contrib_weight is not None and not return_contrib:
@@ -93,6 +194,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     _return_alpha = threading.local()  # set by rasterize_gaussians(..., return_alpha=True) for its one call
     _absgrad = threading.local()       # set by rasterize_gaussians(..., absgrad=True) for its one call
     _contrib = threading.local()       # set by rasterize_gaussians(..., return_contrib=True): (contrib_weight,)
+    _features = threading.local()      # True for a call with features=; the forward replaces it by its buffers
 
     @staticmethod
     def _absgrad_kw(ctx):
@@ -158,6 +260,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         saved = (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning, img)
         ctx.save_for_backward(*saved, *(() if dc is None else (dc,)))
         outs = (color, radii, invdepths, alpha) if with_alpha else (color, radii, invdepths)
+        if getattr(_RasterizeGaussians._features, "value", None) is True:
+            # features=: the buffers saved above are handed to the feature node (rasterize_gaussians), nothing else
+            _RasterizeGaussians._features.value = (geom, binning, img, num_rendered)
         if contrib is None:
             ctx.mark_non_differentiable(radii)
             return outs
@@ -260,14 +365,15 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, dc=None, return_alpha=False, absgrad=False, return_contrib=False,
-                contrib_weight=None):
+                contrib_weight=None, features=None):
         """Same checks as the reference (:242-261).  ``dc=`` (keyword) selects the 3DGS-accel separate-SH
         input: ``dc`` = ``_features_dc`` [P,1,3] and ``shs`` = ``_features_rest`` [P,M,3]
         (gaussian_renderer/__init__.py:115-125).  ``return_alpha=True`` returns ``(color, radii, invdepths,
         alpha)`` with the differentiable accumulated-alpha map [1,H,W] (``rasterize_gaussians``).
         ``absgrad=True``: the backward also sets ``means2D.absgrad`` (``rasterize_gaussians``).
         ``return_contrib=True`` [+ ``contrib_weight=``]: the per-Gaussian contribution statistics [P,4] as the last
-        output (``rasterize_gaussians``)."""
+        output (``rasterize_gaussians``).  ``features=`` [P,C]: one more differentiable output ``feature_map``
+        [C,H,W], after ``alpha`` and before the statistics (``rasterize_gaussians``)."""
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -283,6 +389,8 @@ class GaussianRasterizer(nn.Module):
         # (no keyword at all without the request: the call is then the one without the feature)
         contrib_kw = dict(return_contrib=True, contrib_weight=contrib_weight) if return_contrib else (
             {} if contrib_weight is None else dict(contrib_weight=contrib_weight))
+        if features is not None:
+            contrib_kw = dict(contrib_kw, features=features)
         if dc is None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad, **contrib_kw)

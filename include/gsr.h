@@ -256,6 +256,58 @@ int gsr_contrib_stats(int P, int R, int width, int height, const void* geom_buff
                       const float* pixel_weight /* [H,W] row-major or NULL */, int accumulate,
                       float* stats /* [P,4], 16-byte aligned */, void* stream);
 
+/* N-channel feature rendering (semantic / language feature fields, latent appearance codes, normals, ids: gsplat's
+ * N-D features).  Per-Gaussian feature vectors F [P,C] (float32, any C >= 1) are blended per pixel with the weights
+ * the forward used for the colour, w(g, pix) = alpha(g, pix) T(g, pix) over the (pixel, Gaussian) pairs of
+ * gsr_contrib_stats:
+ *     Fmap[c, pix] = sum_g w(g, pix) F[g, c]                 (no background term, no clamp)
+ * A pass of its own over a finished forward's buffers instead of ceil(C/3) renders with colors_precomp, each of which
+ * would repeat preprocess, binning and the sort.
+ *
+ * gsr_render_features: from the three buffers of a finished forward (any of the three forwards, under every option,
+ *   also one no backward will follow, and copies of the buffers; P, R, width, height, binning_capacity /
+ *   binning_bytes as gsr_rasterize_backward_ex takes them) and features ([P,C], device) into out_features
+ *   ([C,H,W], device), every element written; a pixel no Gaussian reaches is 0.0 exactly, and P == 0 or R == 0 gives
+ *   zeros (the buffers may then be NULL).  The weights depend on the forward's discrete state alone (list order,
+ *   blend masks, last contributors), each pixel is written by one wave and nothing is added atomically: the map is
+ *   bitwise reproducible, and the same bits after a half-tile, a whole-tile ("fwd_quads" 4) or a no_backward
+ *   forward.  Read-only on the buffers and repeatable; a backward of the colour before or after it is unaffected.
+ *   Runs on `stream`, which must be the forward's or ordered behind it.  The census and the stage profiler do not
+ *   apply.  GSR_ERR_ARGUMENT on C <= 0 (or more than 65535 chunks of gsr_render_features_chunk() channels),
+ *   negative or zero sizes, NULL pointers, missing buffers with R > 0, or a binning buffer whose size matches no
+ *   layout for R.
+ * gsr_render_features_backward: the backward of that map for the upstream gradient dL_dout_features ([C,H,W]).
+ *   Writes every element of dL_dfeatures ([P,C]): dL_dF[g, c] = sum_pix w(g, pix) U[c, pix], zero rows for Gaussians
+ *   that never blended.  With view_block != NULL (gsr_view_block_floats(P) floats, 16-byte aligned) it also forms
+ *   the geometry part: with s_g(pix) = sum_c U[c, pix] F[g, c],
+ *     dL/dalpha_g(pix) = T_g s_g - (sum_{h behind g} w_h s_h) / (1 - alpha_g),
+ *   the suffix sum had front to back from out_features (the forward's map, an input), then the render backward's
+ *   chain to the per-Gaussian sums of dL/dmean2D, dL/dopacity and dL/dconic, written as a view block of this loss
+ *   alone: colour and inverse-depth sums zero, flag words from radii and the geometry buffer's SH clamp flags, the
+ *   header from viewmatrix, projmatrix, campos, tan_fovx / tan_fovy and antialiasing.  gsr_gauss_backward_views with
+ *   n_views = 1 turns it into dL/dmeans3D, dL/dopacity, dL/dscales, dL/drotations (its SH outputs are zero: pass a
+ *   zero dc with M = 0); dL/dmeans2D is the first two floats of row g of the block's second sum array, at float
+ *   64 + 4 P + 4 g.  Conventions are the colour's: no gradient through skips, termination or the 0.99 clamp.
+ *   view_block == NULL (frozen geometry): only dL_dfeatures, and out_features, the camera, radii and the scratch
+ *   callback are not used.  scratch_alloc provides 64 bytes per Gaussian plus a bit each with a view block.
+ *   Per-Gaussian sums are added with float atomics, in the hardware's order: not bitwise reproducible.
+ *   Not covered: the feature loss does not reach the camera tensors or the absolute gradient, features have no
+ *   background, the multi-GPU view exchange is not wired, and precomputed cov3D gets no feature geometry gradient
+ *   (gsr_gauss_backward_views needs scales and rotations).
+ * gsr_render_features_chunk: channels one wave blends at once (the kernels' channel chunk). */
+int gsr_render_features(int P, int C, int R, int width, int height, const void* geom_buffer,
+                        const void* binning_buffer, const void* image_buffer, int binning_capacity,
+                        size_t binning_bytes, const float* features /* [P,C] */, float* out_features /* [C,H,W] */,
+                        void* stream);
+int gsr_render_features_backward(int P, int C, int R, int width, int height, const void* geom_buffer,
+                                 const void* binning_buffer, const void* image_buffer, int binning_capacity,
+                                 size_t binning_bytes, const float* features, const float* out_features,
+                                 const float* dL_dout_features, float* dL_dfeatures /* [P,C] */,
+                                 float* view_block /* or NULL */, const float* viewmatrix, const float* projmatrix,
+                                 const float* campos, float tan_fovx, float tan_fovy, int antialiasing,
+                                 const int* radii, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream);
+int gsr_render_features_chunk(void);
+
 /* Multi-GPU view exchange (gaussian_splatting_amd/distributed.py
  * ViewExchange).  The reference trains on one GPU; sharding views over N ranks needs the
  * N views' parameter gradients summed on every rank.  Instead of all-reducing the 59-float
