@@ -876,10 +876,10 @@ __device__ __forceinline__ uint32_t tile_len(uint2 r, u64 cap) {
 }
 
 // Bitonic network in global memory, for lists longer than any register/LDS sort here (any
-// length; slow -- real scenes rarely produce such tiles, and the bucket sort below takes every
-// list up to kBucketMax).  The "flip" form: every comparator is ascending; for block size k the
-// first step pairs i with i ^ (k - 1), the others with i ^ j, so keys past n behave as +infinity
-// and are never touched.
+// length; slow -- it takes the long lists the bucket sort below gives up for skew: tiles whose depths
+// cluster, as a wall seen head-on with a floater in front, tests/test_gpu_depth_skew.py).  The "flip"
+// form: every comparator is ascending; for block size k the first step pairs i with i ^ (k - 1), the
+// others with i ^ j, so keys past n behave as +infinity and are never touched.
 __device__ void sort_list_global(u64* __restrict__ keys, uint32_t lo, uint32_t n, uint32_t* __restrict__ gid_sorted) {
     u64* k = keys + lo;
     uint32_t N2 = 1;
@@ -920,6 +920,7 @@ __device__ void sort_list_global(u64* __restrict__ keys, uint32_t lo, uint32_t n
 // reference's (depth, index) order exactly: keys are compared whole.
 constexpr int kBinShift = 1;       // bins = pow2 >= n >> kBinShift (about two keys per bin)
 constexpr uint32_t kSkew = 48;     // fallback when sum(bin size^2) > kSkew * n
+constexpr uint32_t kSkewBinMax = 1u << 15;  // a bin counts as this many keys at most (bucket_sort_long)
 
 template <int T, int NMAX, int NBMAX>
 struct BucketLds {
@@ -1005,7 +1006,9 @@ __device__ bool bucket_sort_list(const u64* __restrict__ keys, uint32_t lo, uint
     for (int e = 0; e < E; e++)
         if ((uint32_t)e * T + tid < n) o[e] = atomicAdd(&s.start[(uint32_t)((k[e] - mn) >> sh)], 1u);
     __syncthreads();
-    // bin counts -> bin starts (in place), and the sum of squared bin sizes
+    // bin counts -> bin starts (in place), and the sum of squared bin sizes: at most n^2, which 32 bits hold
+    // for every list this function takes (n <= T * E keys; bucket_sort_long, with no such bound, clamps the bins)
+    static_assert((u64)T * E * T * E <= 0xffffffffull, "sum(bin size^2) <= (T * E)^2 fits the 32-bit skew sum");
     uint32_t run = 0, sq = 0;
     for (uint32_t c = 0; c < per; c++) {
         const uint32_t v = s.start[tid * per + c];
@@ -1134,11 +1137,20 @@ __device__ bool bucket_sort_long(const u64* __restrict__ keys, uint32_t lo, uint
             if (i0 + u * T < n) atomicAdd(&s.start[(uint32_t)((k[u] - mn) >> sh)], 1u);
     }
     __syncthreads();
+    // A list here has any length, and unclamped a bin of 65536 keys would add 0 to this 32-bit sum: the list
+    // would pass as flat and leave it to the window check below (which stays) to find the bin that fits no
+    // window.  So a bin counts as kSkewBinMax = 2^15 keys at most: the sum is then at most 2^15 * n, which
+    // cannot wrap for a list under 2^17 keys, and a bin of 2^15 keys or more fails the skew test by itself
+    // (2^30 > kSkew * n up to 22M keys), as with the exact sum every bin over the buffer does
+    // (tests/test_depth_skew_ref.py, tests/test_gpu_depth_skew.py hot_bin_65536).  No list changes its result.
+    // (The sum stays in 32 bits: summed in 64, it cost tile_sort_window_kernel a spilled register and with it
+    // ~4 us a step at 1M@1080p.)
     uint32_t run = 0, sq = 0;
     for (uint32_t c = 0; c < per; c++) {
         const uint32_t v = s.start[tid * per + c];
+        const uint32_t vc = v < kSkewBinMax ? v : kSkewBinMax;
         run += v;
-        sq += v * v;
+        sq += vc * vc;
     }
     uint32_t all = 0;
     uint32_t at = block_exclusive_scan(run, s.tmp, &all);

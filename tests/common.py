@@ -265,6 +265,94 @@ POSE_CASES = [
 ]
 
 
+# Depth-layer scenes: depths that cluster in a sliver of their range, tie exactly, or span the whole key range --
+# what the per-tile bucket sort (binning.hip) gives to its fallback networks, and the near-first cut's histogram
+# sees in one bin.  Built by build_depth from Case.extra["layers"]: (amount, z0, width[, "log"]) per layer, amount
+# a fraction of P (float), a count (int) or None (every Gaussian not yet taken); the layer's Gaussians get the
+# depth z0 + U[0, width) ("log": log-uniform in [z0, width]).  tests/test_depth_skew_ref.py proves from the
+# oracle and tests/sort_model.py what each scene reaches; tests/test_gpu_depth_skew.py runs them.
+# A separate list: tests index SMALL_CASES by position.
+_OUTLIERS = [(0.0025, 2.0, 0.5), (0.0025, 40.0, 10.0)]
+_WALL = dict(W=64, H=64, scale_range=(0.03, 0.15), extra=dict(layers=_OUTLIERS + [(None, 5.0, 1e-4)]))
+_WALL8 = dict(W=32, H=32, scale_range=(0.1, 0.4), extra=dict(layers=[(4, 2.0, 0.5), (4, 40.0, 10.0), (None, 5.0, 1e-4)]))
+_FG_WALL = dict(W=32, H=32, scale_range=(0.1, 0.4),
+                extra=dict(layers=[(0.004, 2.0, 0.1), (0.001, 40.0, 10.0), (None, 5.0, 1e-4)]))
+DEPTH_CASES = [
+    Case("wall_129_256", P=1500, **_WALL),    # tile_sort_kernel's fallbacks: sort_list<64, 4>,
+    Case("wall_257_512", P=4000, **_WALL),    # sort_list<64, 8>
+    Case("wall_513_1024", P=8000, **_WALL),   # and sort_list<64, 16>
+    Case("wall_class0_1k", P=1800, **_WALL8),  # long lists (1024, 4096]: the keys in registers
+    Case("wall_class0_3k", P=5000, **_WALL8),
+    Case("wall_class1", P=10000, W=16, H=16, scale_range=(0.1, 0.4), extra=_WALL8["extra"]),  # one list of 10000
+    # runs of equal depth: the index bits order them (seed 1: with seed 0 the f32 oracle's n_contrib differs from
+    # the f64 oracle's at one pixel, and the GPU tests hold these scenes to exact bars)
+    Case("wall_equal", P=5000, W=32, H=32, scale_range=(0.1, 0.4), seed=1,
+         extra=dict(layers=[(4, 2.0, 0.5), (4, 40.0, 10.0), (None, 5.0, 0.0)])),
+    Case("moderate_pass", P=5000, W=32, H=32, scale_range=(0.1, 0.4), extra=dict(layers=[(0.10, 5.0, 1e-5)])),
+    Case("hot_bin_65536", P=65536 + 8, W=16, H=16,  # one bin of exactly 2^16 keys: its square is 0 mod 2^32
+         extra=dict(layers=[(4, 2.0, 0.5), (4, 40.0, 10.0), (65536, 5.0, 0.0)])),
+    Case("fg_wall_4k", P=4500, **_FG_WALL),   # a near-first cut between a thin foreground and the wall
+    Case("fg_wall_8k", P=8000, **_FG_WALL),
+    Case("depth_extremes", P=5000, W=32, H=32, scale_range=(0.1, 0.4), extra=dict(layers=[(None, 0.2005, 3e4, "log")])),
+]
+
+
+def depth_case(name: str) -> Case:
+    return next(c for c in DEPTH_CASES if c.name == name)
+
+
+def build_depth(case: Case):
+    """build(case) under the identity camera (view-space depth is world z exactly) with the layers' Gaussians moved
+    to their new depths along their view rays: x and y scale by z_new / z_old, so screen positions stay."""
+    assert not is_pose_case(case) and case.yaw == 0.0
+    inp = build(case)
+    means = inp["means3D"].clone()
+    g = torch.Generator().manual_seed(case.seed + 1000)
+    perm = torch.randperm(case.P, generator=g)
+    z_old = means[:, 2].clone()
+    z_new = z_old.clone()
+    at = 0
+    for amount, z0, width, *mode in case.extra["layers"]:
+        cnt = case.P - at if amount is None else amount if isinstance(amount, int) else int(round(amount * case.P))
+        idx = perm[at:at + cnt]
+        at += cnt
+        u = torch.rand(cnt, generator=g)
+        if mode == ["log"]:
+            z_new[idx] = torch.exp(math.log(z0) + u * (math.log(width) - math.log(z0)))
+        else:
+            z_new[idx] = z0 + u * width  # (float32: a width of 1e-4 at z = 5 leaves ~210 distinct depths)
+    assert at <= case.P
+    s = z_new / z_old
+    inp["means3D"] = torch.stack([means[:, 0] * s, means[:, 1] * s, z_new], 1).contiguous()
+    return inp
+
+
+_DEPTH_REFS: dict = {}
+
+
+def depth_reference(name: str):
+    """(case, inputs, f32 oracle result, per-tile key lists) of a depth-layer scene, computed once per process and
+    shared by the tests that use it (read only)."""
+    if name not in _DEPTH_REFS:
+        from tests import sort_model
+
+        case = depth_case(name)
+        inp = build_depth(case)
+        ref = run_oracle(inp)
+        rb = ref.handle.binning()
+        keys = sort_model.tile_keys(ref.handle.geom()["depths"], rb["point_list"], rb["ranges"])
+        _DEPTH_REFS[name] = (case, inp, ref, keys)
+    return _DEPTH_REFS[name]
+
+
+def zbin_of(depths) -> np.ndarray:
+    """The near-first cut's depth bin of float32 depths (csrc/gsr_common.h zbin: 256 bins of 2^19 float codes from
+    0.2, clamped at both ends)."""
+    b = (np.ascontiguousarray(depths, dtype=np.float32).view(np.uint32) >> 19).astype(np.int64)
+    base = int(np.array([0.2], np.float32).view(np.uint32)[0] >> 19)
+    return np.clip(b - base, 0, 255)
+
+
 def pose_case(name: str) -> Case:
     return next(c for c in POSE_CASES if c.name == name)
 

@@ -13,66 +13,7 @@ import random
 
 import pytest
 
-K_BIN_SHIFT = 1
-K_SKEW = 48
-
-
-def bucket_sort_long_model(keys, nmax=2048, nbmax=2048, threads=256, rng=None, lim=None):
-    """Returns the sorted list -- in prefix mode (lim) (its first `sorted` entries, sorted) -- or None where the
-    kernel reports failure (skew, or one bin over the buffer)."""
-    rng = rng or random.Random(0)
-    n = len(keys)
-    mn, mx = min(keys), max(keys)
-    lg = 0
-    while (1 << lg) < (n >> K_BIN_SHIFT) and (1 << lg) < nbmax:
-        lg += 1
-    span = mx - mn
-    bits = span.bit_length() if span else 0
-    sh = bits - lg if bits > lg else 0
-    nb = (span >> sh) + 1
-    per = (nb + threads - 1) // threads
-    start = [0] * (per * threads + 2)
-    for k in keys:
-        start[(k - mn) >> sh] += 1
-    if sum(v * v for v in start[:nb]) > K_SKEW * n:
-        return None
-    at = 0
-    for b in range(per * threads):
-        v = start[b]
-        start[b] = at
-        at += v
-    start[nb] = n
-    out = [None] * n
-    bw0 = w0 = 0
-    lim = n if lim is None else lim
-    while w0 < n and w0 < lim:
-        cut = w0 + nmax
-        w1 = cut if cut < n else n
-        if cut < n:
-            for b in range(bw0, nb):
-                if start[b] < cut < start[b + 1]:
-                    w1 = min(w1, start[b])
-        if w1 <= w0:
-            return None
-        bw1 = min([b for b in range(bw0, nb) if start[b] >= w1], default=nb)
-        buf = [None] * nmax
-        order = list(range(n))
-        rng.shuffle(order)  # the atomics' arrival order is arbitrary
-        for i in order:
-            k = keys[i]
-            b = (k - mn) >> sh
-            if bw0 <= b < bw1:
-                buf[start[b] - w0] = k
-                start[b] += 1
-        for j in range(w1 - w0):
-            kj = buf[j]
-            b = (kj - mn) >> sh
-            st = (start[b - 1] if b else 0) - w0
-            en = start[b] - w0
-            c = sum(1 for q in range(st, en) if buf[q] < kj)
-            out[w0 + st + c] = kj
-        w0, bw0 = w1, bw1
-    return out if lim >= n else (out[:w0], w0)
+from tests.sort_model import bucket_sort_long_model
 
 
 @pytest.mark.parametrize("seed", range(6))
