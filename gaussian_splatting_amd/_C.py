@@ -29,7 +29,7 @@ __all__ = ["rasterize_gaussians", "rasterize_gaussians_backward", "rasterize_gau
            "render_features", "render_features_backward", "feature_chunk", "check_features"]
 
 
-# Sync-free forward (gsr_rasterize_forward_ex): the binning buffer is sized from a capacity
+# Sync-free forward (gsr_forward_args.capacity_hint): the binning buffer is sized from a capacity
 # hint -- a decaying maximum of recent num_rendered for the same (device, W, H) and point
 # count, plus a margin -- so the forward never waits for the host mid-way.  A hint that
 # turns out too small only costs a redo of the binning stage inside the library
@@ -312,6 +312,45 @@ def render_features_backward(geomBuffer: torch.Tensor, binningBuffer: torch.Tens
     return dL_dF, block
 
 
+def _scene_view(ins: _Inputs, *, means3D, dc, sh, degree, colors, opacities, scales, scale_modifier, rotations,
+                cov3D_precomp, background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, W, H, antialiasing,
+                align_sh=False):
+    """The ``Scene`` and ``View`` every rasterizer call passes (include/gsr.h gsr_scene / gsr_view), from the
+    tensors, validated and kept alive by ``ins``.  ``dc`` goes in only with SH colours (the split layout); an empty
+    optional tensor is absent; ``campos`` may live on the host."""
+    split = dc is not None and _present(dc) and not _present(colors)
+    if campos is not None and campos.device.type != "cuda":
+        campos = campos.to(ins.device)
+    # (pointers are taken in the reference's argument order: the first malformed tensor is the one reported)
+    p_bg = ins.req(background, "bg", small=True)
+    scene = _lib.Scene(
+        P=means3D.size(0), D=int(degree), M=sh.size(1) if _present(sh) else 0, means3D=ins.req(means3D, "means3D"),
+        dc=ins.req(dc, "dc") if split else None, shs=ins.opt(sh, "sh", align16=align_sh),
+        colors_precomp=ins.opt(colors, "colors_precomp"), opacities=ins.req(opacities, "opacities"),
+        scales=ins.opt(scales, "scales"), scale_modifier=float(scale_modifier),
+        rotations=ins.opt(rotations, "rotations", align16=True), cov3D_precomp=ins.opt(cov3D_precomp, "cov3D_precomp"))
+    view = _lib.View(
+        width=W, height=H, background=p_bg, viewmatrix=ins.req(viewmatrix, "viewmatrix", small=True),
+        projmatrix=ins.req(projmatrix, "projmatrix", small=True), campos=ins.opt(campos, "campos"),
+        tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy), antialiasing=int(bool(antialiasing)))
+    return scene, view
+
+
+def _unpack_backward(args, who: str) -> tuple:
+    """The vendored rasterizer's 24 positional backward arguments, or the 3DGS-accel build's 25 with ``dc`` before
+    ``sh``: always the 25 (``dc`` None for 24), then whether it was the accel form."""
+    if len(args) == 25:
+        return (*args, True)
+    if len(args) != 24:
+        raise TypeError(f"{who}(): expected 24 or 25 positional arguments, got {len(args)}")
+    (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+     projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, sh, degree, campos, geomBuffer, R,
+     binningBuffer, imageBuffer, antialiasing, debug) = args
+    return (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp,
+            viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, None, sh, degree, campos,
+            geomBuffer, R, binningBuffer, imageBuffer, antialiasing, debug, False)
+
+
 def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = False) -> tuple:
     """RasterizeGaussiansCUDA (rasterize_points.cu:45-146).
 
@@ -319,7 +358,7 @@ def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = F
     ``(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
     tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, antialiasing, debug)``
     -- the vendored rasterizer's 20 -- or the 3DGS-accel build's 21, which insert ``dc`` ([P,1,3]) before ``sh``
-    (then the rest coefficients [P,M,3]); see include/gsr.h gsr_rasterize_forward_dc.
+    (then the rest coefficients [P,M,3]); see include/gsr.h gsr_scene.dc.
 
     Returns ``(num_rendered, color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer, invdepth[1,H,W])``.
 
@@ -361,38 +400,31 @@ def rasterize_gaussians(*args, no_backward: bool = False, return_alpha: bool = F
         fwd = (0, out_color, radii, geom, binning, img, out_invdepth)
         return fwd + (torch.zeros((1, H, W), **f32),) if return_alpha else fwd
 
-    M = sh.size(1) if _present(sh) else 0
-    split = dc is not None and _present(dc) and not _present(colors)
     ins = _Inputs(device)
     rg, rb, ri = _Resizer(geom), _Resizer(binning), _Resizer(img)
-    nr = ctypes.c_int(0)
-    cap = ctypes.c_int(0)
     key = (device.index, W, H)
-    common_head = (rg.cb, None, rb.cb, None, ri.cb, None, P, int(degree), M,
-                   ins.req(background, "bg", small=True), W, H, ins.req(means3D, "means3D"))
-    sh_args = ((ins.req(dc, "dc"), ins.opt(sh, "sh", align16=True)) if split else (ins.opt(sh, "sh", align16=True),))
-    common_tail = (
-        ins.opt(colors, "colors_precomp"), ins.req(opacity, "opacities"), ins.opt(scales, "scales"),
-        float(scale_modifier), ins.opt(rotations, "rotations", align16=True), ins.opt(cov3D_precomp, "cov3D_precomp"),
-        ins.req(viewmatrix, "viewmatrix", small=True), ins.req(projmatrix, "projmatrix", small=True),
-        ins.opt(campos if campos is not None and campos.device.type == "cuda" else
-                (campos.to(device) if campos is not None else None), "campos"),
-        float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), out_color.data_ptr(), out_invdepth.data_ptr(),
-        int(bool(antialiasing)), radii.data_ptr(), int(bool(debug)), _stream_handle(device), ctypes.byref(nr),
-        _capacity_hint(key, P), ctypes.byref(cap))
-    fn = lib.gsr_rasterize_forward_dc if split else lib.gsr_rasterize_forward_ex
+    scene, view = _scene_view(
+        ins, means3D=means3D, dc=dc, sh=sh, degree=degree, colors=colors, opacities=opacity, scales=scales,
+        scale_modifier=scale_modifier, rotations=rotations, cov3D_precomp=cov3D_precomp, background=background,
+        viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, W=W, H=H,
+        antialiasing=antialiasing, align_sh=True)
+    a = _lib.ForwardArgs(
+        scene=scene, view=view, geom_alloc=rg.cb, binning_alloc=rb.cb, image_alloc=ri.cb,
+        prefiltered=int(bool(prefiltered)), debug=int(bool(debug)), stream=_stream_handle(device),
+        out_color=out_color.data_ptr(), out_invdepth=out_invdepth.data_ptr(), radii=radii.data_ptr(),
+        capacity_hint=_capacity_hint(key, P))
     with torch.cuda.device(device):
         if no_backward:
             with _lib.thread_options(bwd_atomic=0):
-                rc = fn(*common_head, *sh_args, *common_tail)
+                rc = lib.gsr_rasterize_forward(ctypes.byref(a))
         else:
-            rc = fn(*common_head, *sh_args, *common_tail)
+            rc = lib.gsr_rasterize_forward(ctypes.byref(a))
     _lib.check(rc, "rasterize_gaussians")
     _FORWARD_GEOMS[geom.data_ptr()] = geom
-    _note_rendered(key, P, nr.value)
+    _note_rendered(key, P, a.num_rendered)
     # The binning buffer's layout (its capacity) is recovered by the backward from the buffer's
-    # size (include/gsr.h gsr_rasterize_backward_ex), so nothing rides on the tensor object.
-    fwd = (int(nr.value), out_color, radii, geom, binning, img, out_invdepth)
+    # size (include/gsr.h gsr_backward_args.binning_bytes), so nothing rides on the tensor object.
+    fwd = (int(a.num_rendered), out_color, radii, geom, binning, img, out_invdepth)
     return fwd + (render_alpha(img, H, W),) if return_alpha else fwd
 
 
@@ -415,25 +447,16 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
     ``tensor.contiguous().view(-1)[k]``.
     ``dL_dout_alpha`` (an extension): the gradient [1,H,W] of the accumulated-alpha output
     (``rasterize_gaussians(..., return_alpha=True)``); its share is added to every returned gradient it reaches
-    (include/gsr.h gsr_rasterize_backward_alpha) and, with ``camera=True``, to the camera gradients.  None or
+    (include/gsr.h gsr_backward_args.dL_dalphas) and, with ``camera=True``, to the camera gradients.  None or
     an empty tensor: no alpha loss, the call and its results are those without the keyword.
     ``absgrad=True`` (an extension): the absolute screen-space gradient [P,3] (include/gsr.h
-    gsr_rasterize_backward_abs: per Gaussian the sum over pixels of the absolute value of each pixel's term of
+    gsr_backward_args.dL_dmean2D_abs: per Gaussian the sum over pixels of the absolute value of each pixel's term of
     ``dL_dmeans2D``, column 2 zero) is appended as the LAST element of the returned tuple, after the camera
     gradients when ``camera=True``.  Without it the call and its results are those without the keyword.
     """
-    if len(args) == 25:
-        (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-         projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, dc, sh, degree, campos, geomBuffer, R,
-         binningBuffer, imageBuffer, antialiasing, debug) = args
-        accel = True
-    elif len(args) == 24:
-        (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-         projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, sh, degree, campos, geomBuffer, R,
-         binningBuffer, imageBuffer, antialiasing, debug) = args
-        dc, accel = None, False
-    else:
-        raise TypeError(f"rasterize_gaussians_backward(): expected 24 or 25 positional arguments, got {len(args)}")
+    (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+     projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, dc, sh, degree, campos, geomBuffer, R,
+     binningBuffer, imageBuffer, antialiasing, debug, accel) = _unpack_backward(args, "rasterize_gaussians_backward")
     _require_device(means3D, "means3D")
     device = means3D.device
     lib = _lib.load()
@@ -483,46 +506,30 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
     scratch = torch.empty(0, dtype=torch.uint8, device=device)
     rs = _Resizer(scratch)
     _own_geometry(geomBuffer)
-    head = (P, int(degree), M, int(R), ins.req(background, "bg", small=True), W, H, ins.req(means3D, "means3D"))
-    sh_args = ((ins.req(dc, "dc"), ins.opt(sh, "sh")) if split else (ins.opt(sh, "sh"),))
-    mid = (ins.opt(colors, "colors_precomp"),
-           ins.req(opacities, "opacities"), ins.opt(scales, "scales"), float(scale_modifier),
-           ins.opt(rotations, "rotations", align16=True), ins.opt(cov3D_precomp, "cov3D_precomp"),
-           ins.req(viewmatrix, "viewmatrix", small=True), ins.req(projmatrix, "projmatrix", small=True),
-           ins.opt(campos if campos is not None and campos.device.type == "cuda" else
-                   (campos.to(device) if campos is not None else None), "campos"),
-           float(tan_fovx), float(tan_fovy), ins.radii(radii), geomBuffer.data_ptr(),
-           binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
-           ins.req(dL_dout_color, "dL_dout_color"),
-           ins.req(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
-           dL_dmeans2D.data_ptr(), dL_dconic.data_ptr() if camera else None, dL_dopacity.data_ptr(),
-           dL_dcolors.data_ptr(),
-           dL_dinvdepths.data_ptr() if has_inv else None, dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr())
-    sh_grads = ((dL_ddc.data_ptr(), dL_dsh.data_ptr() if M > 0 else None) if split else
-                (dL_dsh.data_ptr() if M > 0 else None,))
-    tail = (dL_dscales.data_ptr(), dL_drotations.data_ptr(), int(bool(antialiasing)), int(bool(debug)), rs.cb, None,
-            _stream_handle(device), 0, int(binningBuffer.numel()))
     has_alpha = dL_dout_alpha is not None and dL_dout_alpha.numel() != 0
     if has_alpha and dL_dout_alpha.numel() != H * W:
         raise RuntimeError(f"dL_dout_alpha: expected {(1, H, W)} values, got {tuple(dL_dout_alpha.shape)}")
-    if has_alpha or absgrad:
-        # gsr_rasterize_backward_alpha: the _dc argument list (dc NULL = combined shs) with dL_dalphas after
-        # dL_dinvdepths; gsr_rasterize_backward_abs: the same with dL_dmean2D_abs at the end
-        n_in = 17  # mid: the inputs and upstream gradients up to dL_dinvdepths
-        sh_in = sh_args if split else (None,) + sh_args
-        sh_out = sh_grads if split else (None,) + sh_grads
-        p_alpha = ins.req(dL_dout_alpha, "dL_dout_alpha") if has_alpha else None
-        with torch.cuda.device(device):
-            if absgrad:
-                rc = lib.gsr_rasterize_backward_abs(*head, *sh_in, *mid[:n_in], p_alpha, *mid[n_in:], *sh_out, *tail,
-                                                    dL_dabs.data_ptr())
-            else:
-                rc = lib.gsr_rasterize_backward_alpha(*head, *sh_in, *mid[:n_in], p_alpha, *mid[n_in:], *sh_out,
-                                                      *tail)
-    else:
-        fn = lib.gsr_rasterize_backward_dc if split else lib.gsr_rasterize_backward_ex
-        with torch.cuda.device(device):
-            rc = fn(*head, *sh_args, *mid, *sh_grads, *tail)
+    scene, view = _scene_view(
+        ins, means3D=means3D, dc=dc, sh=sh, degree=degree, colors=colors, opacities=opacities, scales=scales,
+        scale_modifier=scale_modifier, rotations=rotations, cov3D_precomp=cov3D_precomp, background=background,
+        viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, W=W, H=H,
+        antialiasing=antialiasing)
+    a = _lib.BackwardArgs(
+        scene=scene, view=view, R=int(R), radii=ins.radii(radii), geom_buffer=geomBuffer.data_ptr(),
+        binning_buffer=binningBuffer.data_ptr() if binningBuffer.numel() else None,
+        image_buffer=imageBuffer.data_ptr(), binning_capacity=0, binning_bytes=int(binningBuffer.numel()),
+        dL_dpix=ins.req(dL_dout_color, "dL_dout_color"),
+        dL_dinvdepths=ins.req(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
+        dL_dalphas=ins.req(dL_dout_alpha, "dL_dout_alpha") if has_alpha else None,
+        dL_dmean2D=dL_dmeans2D.data_ptr(), dL_dmean2D_abs=dL_dabs.data_ptr() if absgrad else None,
+        dL_dconic=dL_dconic.data_ptr() if camera else None, dL_dopacity=dL_dopacity.data_ptr(),
+        dL_dcolor=dL_dcolors.data_ptr(), dL_dinvdepth=dL_dinvdepths.data_ptr() if has_inv else None,
+        dL_dmean3D=dL_dmeans3D.data_ptr(), dL_dcov3D=dL_dcov3D.data_ptr(),
+        dL_ddc=dL_ddc.data_ptr() if split else None, dL_dsh=dL_dsh.data_ptr() if M > 0 else None,
+        dL_dscale=dL_dscales.data_ptr(), dL_drot=dL_drotations.data_ptr(), debug=int(bool(debug)),
+        scratch_alloc=rs.cb, stream=_stream_handle(device))
+    with torch.cuda.device(device):
+        rc = lib.gsr_rasterize_backward(ctypes.byref(a))
     _lib.check(rc, "rasterize_gaussians_backward")
     if not camera:
         return result + (dL_dabs,) if absgrad else result
@@ -530,15 +537,15 @@ def rasterize_gaussians_backward(*args, out=None, camera=False, dL_dout_alpha=No
     dL_dview, dL_dproj, dL_dcampos = _empty((4, 4), **f32), _empty((4, 4), **f32), _empty((3,), **f32)
     cam_scratch = torch.empty(0, dtype=torch.uint8, device=device)
     rc_s = _Resizer(cam_scratch)
-    (p_colors, p_opac, p_scales, _mod, p_rot, p_cov, p_view, p_proj, p_campos, _tx, _ty, p_radii) = mid[:12]
-    p_dc, p_sh = (None, None) if p_colors else (sh_args if split else (None, sh_args[0]))
+    # (with precomputed colours the camera backward takes no SH input)
+    p_dc, p_sh = (None, None) if scene.colors_precomp else (scene.dc, scene.shs)
     with torch.cuda.device(device):
         rc = lib.gsr_camera_backward(
-            P, int(degree), M, W, H, head[-1], p_dc, p_sh, p_colors, p_opac, p_scales, float(scale_modifier), p_rot,
-            p_cov, p_view, p_proj, p_campos, float(tan_fovx), float(tan_fovy), p_radii, geomBuffer.data_ptr(),
-            dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(), dL_dcolors.data_ptr(),
-            dL_dinvdepths.data_ptr() if has_inv else None, int(bool(antialiasing)), rc_s.cb, None,
-            _stream_handle(device), dL_dview.data_ptr(), dL_dproj.data_ptr(), dL_dcampos.data_ptr())
+            P, scene.D, scene.M, W, H, scene.means3D, p_dc, p_sh, scene.colors_precomp, scene.opacities, scene.scales,
+            scene.scale_modifier, scene.rotations, scene.cov3D_precomp, view.viewmatrix, view.projmatrix, view.campos,
+            view.tan_fovx, view.tan_fovy, a.radii, a.geom_buffer, a.dL_dmean2D, a.dL_dconic, a.dL_dopacity,
+            a.dL_dcolor, a.dL_dinvdepth, view.antialiasing, rc_s.cb, None, _stream_handle(device),
+            dL_dview.data_ptr(), dL_dproj.data_ptr(), dL_dcampos.data_ptr())
     _lib.check(rc, "camera_backward")
     result = result + (dL_dview, dL_dproj, dL_dcampos)
     return result + (dL_dabs,) if absgrad else result
@@ -713,21 +720,14 @@ def views_live_list(flags: torch.Tensor, live: torch.Tensor, P: int, rng=None) -
 def rasterize_gaussians_backward_screen(*args, view_block: torch.Tensor) -> None:
     """The backward of ``rasterize_gaussians_backward`` up to the per-Gaussian render-gradient
     sums, written with the camera into ``view_block`` (a float32 tensor of
-    ``view_block_floats(P)`` values; include/gsr.h ``gsr_rasterize_backward_screen``).
+    ``view_block_floats(P)`` values; include/gsr.h ``gsr_backward_args.view_block``).
     Arguments as ``rasterize_gaussians_backward`` (24, or 25 with ``dc``); colours from SH and
     cov3D from scales / rotations.  The rest of the backward, over any number of gathered
     views, is ``gauss_backward_views``."""
-    if len(args) == 25:
-        (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-         projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, dc, sh, degree, campos, geomBuffer, R,
-         binningBuffer, imageBuffer, antialiasing, debug) = args
-    elif len(args) == 24:
-        (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-         projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, sh, degree, campos, geomBuffer, R,
-         binningBuffer, imageBuffer, antialiasing, debug) = args
-        dc = None
-    else:
-        raise TypeError(f"rasterize_gaussians_backward_screen(): expected 24 or 25 positional arguments, got {len(args)}")
+    (background, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+     projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_invdepth, dc, sh, degree, campos, geomBuffer, R,
+     binningBuffer, imageBuffer, antialiasing, debug, _accel) = _unpack_backward(
+         args, "rasterize_gaussians_backward_screen")
     if _present(colors) or _present(cov3D_precomp):
         raise RuntimeError("rasterize_gaussians_backward_screen: precomputed colours / cov3D are per view; "
                            "use rasterize_gaussians_backward")
@@ -740,27 +740,27 @@ def rasterize_gaussians_backward_screen(*args, view_block: torch.Tensor) -> None
         raise RuntimeError(f"view_block must be a contiguous float32 tensor of {nb} values on {device}")
     if P == 0:
         return
-    lib = _lib.load()
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = sh.size(1) if _present(sh) else 0
     has_inv = dL_dout_invdepth is not None and dL_dout_invdepth.numel() != 0 and dL_dout_invdepth.size(0) != 0
     ins = _Inputs(device)
     scratch = torch.empty(0, dtype=torch.uint8, device=device)
     rs = _Resizer(scratch)
     _own_geometry(geomBuffer)
+    scene, view = _scene_view(
+        ins, means3D=means3D, dc=dc, sh=sh, degree=degree, colors=None, opacities=opacities, scales=scales,
+        scale_modifier=scale_modifier, rotations=rotations, cov3D_precomp=None, background=background,
+        viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, W=W, H=H,
+        antialiasing=antialiasing)
+    a = _lib.BackwardArgs(
+        scene=scene, view=view, R=int(R), radii=ins.radii(radii), geom_buffer=geomBuffer.data_ptr(),
+        binning_buffer=binningBuffer.data_ptr() if binningBuffer.numel() else None,
+        image_buffer=imageBuffer.data_ptr(), binning_capacity=0, binning_bytes=int(binningBuffer.numel()),
+        dL_dpix=ins.req(dL_dout_color, "dL_dout_color"),
+        dL_dinvdepths=ins.req(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
+        view_block=view_block.data_ptr(), debug=int(bool(debug)), scratch_alloc=rs.cb,
+        stream=_stream_handle(device))
     with torch.cuda.device(device):
-        rc = lib.gsr_rasterize_backward_screen(
-            P, int(degree), M, int(R), ins.req(background, "bg", small=True), W, H, ins.req(means3D, "means3D"),
-            ins.opt(dc, "dc") if _present(dc) else None, ins.opt(sh, "sh"), ins.req(opacities, "opacities"),
-            ins.req(scales, "scales"), float(scale_modifier), ins.req(rotations, "rotations", align16=True),
-            ins.req(viewmatrix, "viewmatrix", small=True), ins.req(projmatrix, "projmatrix", small=True),
-            ins.req(campos if campos.device.type == "cuda" else campos.to(device), "campos"),
-            float(tan_fovx), float(tan_fovy), ins.radii(radii), geomBuffer.data_ptr(),
-            binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
-            ins.req(dL_dout_color, "dL_dout_color"),
-            ins.req(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
-            int(bool(antialiasing)), int(bool(debug)), rs.cb, None, _stream_handle(device),
-            0, int(binningBuffer.numel()), view_block.data_ptr())
+        rc = _lib.load().gsr_rasterize_backward(ctypes.byref(a))
     _lib.check(rc, "rasterize_gaussians_backward_screen")
 
 

@@ -48,35 +48,57 @@ class DensifyParams(ctypes.Structure):
                 ("split_n", ctypes.c_int), ("split_div", ctypes.c_float)]
 
 
+# The rasterizer's argument structs (include/gsr.h); tests/test_abi_layout.py holds every field's offset and size
+# against a C program's offsetof / sizeof.
+class Scene(ctypes.Structure):
+    """gsr_scene."""
+
+    _fields_ = [("P", _i), ("D", _i), ("M", _i), ("means3D", _vp), ("dc", _vp), ("shs", _vp),
+                ("colors_precomp", _vp), ("opacities", _vp), ("scales", _vp), ("scale_modifier", _f),
+                ("rotations", _vp), ("cov3D_precomp", _vp)]
+
+
+class View(ctypes.Structure):
+    """gsr_view."""
+
+    _fields_ = [("width", _i), ("height", _i), ("background", _vp), ("viewmatrix", _vp), ("projmatrix", _vp),
+                ("campos", _vp), ("tan_fovx", _f), ("tan_fovy", _f), ("antialiasing", _i)]
+
+
+class _Args(ctypes.Structure):
+    """An argument struct whose first field is its own sizeof (the struct_size rule of include/gsr.h)."""
+
+    def __init__(self, **fields):
+        super().__init__(struct_size=ctypes.sizeof(self), **fields)
+
+
+class ForwardArgs(_Args):
+    """gsr_forward_args."""
+
+    _fields_ = [("struct_size", ctypes.c_size_t), ("scene", Scene), ("view", View),
+                ("geom_alloc", ALLOC_FN), ("geom_ctx", _vp), ("binning_alloc", ALLOC_FN), ("binning_ctx", _vp),
+                ("image_alloc", ALLOC_FN), ("image_ctx", _vp), ("prefiltered", _i), ("debug", _i), ("stream", _vp),
+                ("out_color", _vp), ("out_invdepth", _vp), ("radii", _vp), ("capacity_hint", _i),
+                ("num_rendered", _i), ("binning_capacity", _i)]
+
+
+class BackwardArgs(_Args):
+    """gsr_backward_args."""
+
+    _fields_ = [("struct_size", ctypes.c_size_t), ("scene", Scene), ("view", View), ("R", _i), ("radii", _vp),
+                ("geom_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("binning_capacity", _i),
+                ("binning_bytes", ctypes.c_size_t), ("dL_dpix", _vp), ("dL_dinvdepths", _vp), ("dL_dalphas", _vp),
+                ("dL_dmean2D", _vp), ("dL_dmean2D_abs", _vp), ("dL_dconic", _vp), ("dL_dopacity", _vp),
+                ("dL_dcolor", _vp), ("dL_dinvdepth", _vp), ("dL_dmean3D", _vp), ("dL_dcov3D", _vp), ("dL_ddc", _vp),
+                ("dL_dsh", _vp), ("dL_dscale", _vp), ("dL_drot", _vp), ("view_block", _vp), ("debug", _i),
+                ("scratch_alloc", ALLOC_FN), ("scratch_ctx", _vp), ("stream", _vp)]
+
+
 # argument lists, in include/gsr.h order
 SIGNATURES = {
-    "gsr_rasterize_forward": (_i, [ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp,
-                                   _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i, _vp, _i,
-                                   _vp, ctypes.POINTER(_i)]),
-    "gsr_rasterize_backward": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp,
-                                    _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _i, _i, ALLOC_FN, _vp, _vp]),
-    "gsr_rasterize_forward_ex": (_i, [ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp,
-                                      _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i, _vp, _i,
-                                      _vp, ctypes.POINTER(_i), _i, ctypes.POINTER(_i)]),
-    "gsr_rasterize_backward_ex": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp,
-                                       _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _vp, _vp, _i, _i, ALLOC_FN, _vp, _vp, _i, ctypes.c_size_t]),
-    "gsr_rasterize_forward_dc": (_i, [ALLOC_FN, _vp, ALLOC_FN, _vp, ALLOC_FN, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp,
-                                      _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _i, _vp,
-                                      _i, _vp, ctypes.POINTER(_i), _i, ctypes.POINTER(_i)]),
-    "gsr_rasterize_backward_dc": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp,
-                                       _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _vp, _vp, _vp, _vp, _i, _i, ALLOC_FN, _vp, _vp, _i, ctypes.c_size_t]),
+    "gsr_rasterize_forward": (_i, [ctypes.POINTER(ForwardArgs)]),
+    "gsr_rasterize_backward": (_i, [ctypes.POINTER(BackwardArgs)]),
     "gsr_render_alpha": (_i, [_i, _i, _vp, _vp, _vp]),
-    "gsr_rasterize_backward_alpha": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
-                                          _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ALLOC_FN, _vp, _vp, _i,
-                                          ctypes.c_size_t]),
-    "gsr_rasterize_backward_abs": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
-                                        _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ALLOC_FN, _vp, _vp, _i,
-                                        ctypes.c_size_t, _vp]),
     "gsr_contrib_stats": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_size_t, _vp, _i, _vp, _vp]),
     "gsr_render_features": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_size_t, _vp, _vp, _vp]),
     "gsr_render_features_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_size_t, _vp, _vp, _vp, _vp,
@@ -96,9 +118,6 @@ SIGNATURES = {
     "gsr_view_block_index": (_i, [_i, _i, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp]),
     "gsr_views_live_floats": (ctypes.c_ulonglong, [_i]),
     "gsr_views_live_list": (_i, [_i, _i, _vp, _vp, _vp]),
-    "gsr_rasterize_backward_screen": (_i, [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp,
-                                           _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ALLOC_FN, _vp, _vp, _i,
-                                           ctypes.c_size_t, _vp]),
     "gsr_gauss_backward_views": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, ctypes.c_longlong, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsr_gauss_backward_views_packed": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, ctypes.c_longlong,

@@ -151,7 +151,7 @@ gsr::BinningState carve_binning(char* base, size_t C, size_t* total) {
     return b;
 }
 
-// Binning capacities of the _ex / _dc forwards are multiples of kCapQuantum.  Over those the
+// The forward's binning capacities are multiples of kCapQuantum (up to INT_MAX).  Over those the
 // buffer size is strictly increasing (the keys alone grow by 8 * kCapQuantum bytes a step) and
 // every sub-array's length depends on C / kCkStride at most, so the size of the binning buffer
 // identifies its layout: the backward recovers the capacity from the tensor's byte count, which
@@ -169,7 +169,7 @@ size_t binning_bytes_for(size_t C) {
 
 // Capacity the binning buffer of a forward was laid out for: the explicit value if given,
 // else the multiple of kCapQuantum whose layout has exactly `bytes` bytes, else R (the exact
-// layout of gsr_rasterize_forward).  Returns false if `bytes` matches no layout holding R.
+// layout, which the forward keeps past INT_MAX).  Returns false if `bytes` matches no layout holding R.
 bool resolve_capacity(int R, int capacity, size_t bytes, size_t* C) {
     if (capacity > 0) {
         *C = (size_t)capacity;
@@ -614,18 +614,38 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
 }
 
 namespace {
-int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                 gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width,
-                 int height, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                 const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                 const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                 float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_invdepth,
-                 int antialiasing, int* radii, int debug, void* stream_, int* num_rendered, int capacity_hint,
-                 int* binning_capacity, bool quantized = true) {
+// The struct_size rule of include/gsr.h: nothing but that field is read from a struct of another size.
+int check_struct(const char* who, const void* args, size_t got, size_t want) {
+    if (!args) return fail(GSR_ERR_ARGUMENT, "%s: null argument struct", who);
+    if (got != want)
+        return fail(GSR_ERR_ARGUMENT, "%s: struct_size %zu is not this library's %zu (built from another gsr.h?)", who,
+                    got, want);
+    return GSR_OK;
+}
+
+int forward_impl(gsr_forward_args* args) {
     using namespace gsr;
     HostTimer host_time(g_fwd_host);
     clear_error();
-    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_struct("rasterize_forward", args, args ? args->struct_size : 0, sizeof(gsr_forward_args)))
+        return rc;
+    const gsr_scene& scene = args->scene;
+    const gsr_view& view = args->view;
+    const int P = scene.P, D = scene.D, width = view.width, height = view.height;
+    const float *means3D = scene.means3D, *dc = scene.dc, *shs = scene.shs, *colors_precomp = scene.colors_precomp,
+                *opacities = scene.opacities, *scales = scene.scales, *rotations = scene.rotations,
+                *cov3D_precomp = scene.cov3D_precomp;
+    const float scale_modifier = scene.scale_modifier, tan_fovx = view.tan_fovx, tan_fovy = view.tan_fovy;
+    const float *background = view.background, *viewmatrix = view.viewmatrix, *projmatrix = view.projmatrix,
+                *cam_pos = view.campos;
+    const int antialiasing = view.antialiasing, prefiltered = args->prefiltered, debug = args->debug,
+              capacity_hint = args->capacity_hint;
+    const gsr_alloc_fn geom_alloc = args->geom_alloc, binning_alloc = args->binning_alloc,
+                       image_alloc = args->image_alloc;
+    void *const geom_ctx = args->geom_ctx, *const binning_ctx = args->binning_ctx, *const image_ctx = args->image_ctx;
+    float *const out_color = args->out_color, *const out_invdepth = args->out_invdepth;
+    int* const radii = args->radii;
+    hipStream_t stream = (hipStream_t)args->stream;
     // every option is read ONCE per call: gsr_option_set may run on another thread, and the launches
     // of one forward (K4's prefix and the redo, the render's part protocol, the work list's segment
     // length) must agree with each other
@@ -637,14 +657,14 @@ int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_a
     // K3 writes the record path's inputs only when this forward's backwards may take it without a prep
     const bool k3_recs = !opt_atomic;
     const int opt_near_mass = option(OPT_NEAR_MASS);
-    // _ex / _dc forwards lay the binning buffer out for a multiple of kCapQuantum (the backward
-    // recovers it from the buffer's size); gsr_rasterize_forward keeps the exact C = R layout
-    const auto capacity_for = [quantized](size_t c) {
+    // the binning buffer is laid out for a multiple of kCapQuantum (the backward recovers it from the
+    // buffer's size); only a capacity whose rounding passes INT_MAX keeps the exact layout
+    const auto capacity_for = [](size_t c) {
         const size_t q = quantize_capacity(c);
-        return quantized && q <= (size_t)INT_MAX ? q : c;
+        return q <= (size_t)INT_MAX ? q : c;
     };
-    if (num_rendered) *num_rendered = 0;
-    if (binning_capacity) *binning_capacity = 0;
+    args->num_rendered = 0;
+    args->binning_capacity = 0;
     if (P < 0 || width <= 0 || height <= 0)
         return fail(GSR_ERR_ARGUMENT, "rasterize_forward: invalid sizes P=%d W=%d H=%d", P, width, height);
     if (P >= kMaxGaussians)
@@ -655,8 +675,9 @@ int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_a
         return fail(GSR_ERR_ARGUMENT, "rasterize_forward: missing required input");
     if (!colors_precomp && !shs && !dc)
         return fail(GSR_ERR_ARGUMENT, "rasterize_forward: provide either SHs or precomputed colours");
-    if (dc && M > 0 && !shs) return fail(GSR_ERR_ARGUMENT, "rasterize_forward: %d rest SH coefficients but no shs", M);
-    if (dc) M += 1;  // split layout: M counted the rest; the kernels see dc as coefficient 0
+    if (dc && scene.M > 0 && !shs)
+        return fail(GSR_ERR_ARGUMENT, "rasterize_forward: %d rest SH coefficients but no shs", scene.M);
+    const int M = dc ? scene.M + 1 : scene.M;  // split layout: scene.M counts the rest; the kernels see dc as coefficient 0
     if (!cov3D_precomp && (!scales || !rotations))
         return fail(GSR_ERR_ARGUMENT, "rasterize_forward: provide scales+rotations or a precomputed covariance");
     if (!colors_precomp && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
@@ -878,41 +899,13 @@ int forward_impl(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_a
             if (int rc = bin_and_render(C, false)) return rc;
         }
     }
-    if (num_rendered) *num_rendered = (int)total;
-    if (binning_capacity) *binning_capacity = (int)C;
+    args->num_rendered = (int)total;
+    args->binning_capacity = (int)C;
     return GSR_OK;
 }
 }  // namespace
 
-int gsr_rasterize_forward(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                          gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
-                          int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
-                          const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                          const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
-                          float* out_invdepth, int antialiasing, int* radii, int debug, void* stream,
-                          int* num_rendered) {
-    return forward_impl(geom_alloc, geom_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background,
-                        width, height, means3D, nullptr, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                        out_invdepth, antialiasing, radii, debug, stream, num_rendered, 0, nullptr, false);
-}
-
-int gsr_rasterize_forward_ex(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                             gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
-                             int width, int height, const float* means3D, const float* shs,
-                             const float* colors_precomp, const float* opacities, const float* scales,
-                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                             const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                             float tan_fovy, int prefiltered, float* out_color, float* out_invdepth, int antialiasing,
-                             int* radii, int debug, void* stream, int* num_rendered, int capacity_hint,
-                             int* binning_capacity) {
-    return forward_impl(geom_alloc, geom_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background,
-                        width, height, means3D, nullptr, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                        out_invdepth, antialiasing, radii, debug, stream, num_rendered, capacity_hint,
-                        binning_capacity);
-}
+int gsr_rasterize_forward(gsr_forward_args* args) { return forward_impl(args); }
 
 namespace {
 // The backward's dense outputs are zero-filled on a side stream that runs beside render_bwd
@@ -947,23 +940,45 @@ SideStream* side_stream() {
     return r.ok ? &r : nullptr;
 }
 
-int backward_impl(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
-                  const float* dc, const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
-                  float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                  const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                  void* geom_buffer, void* binning_buffer, void* image_buffer, const float* dL_dpix,
-                  const float* dL_dinvdepths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                  float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc,
-                  float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                  void* scratch_ctx, void* stream_, int binning_capacity, size_t binning_bytes,
-                  const float* dL_dalphas = nullptr, float* view_block = nullptr, float* dL_dmean2D_abs = nullptr) {
+int backward_impl(const gsr_backward_args* args) {
     using namespace gsr;
     HostTimer host_time(g_bwd_host);
     clear_error();
-    hipStream_t stream = (hipStream_t)stream_;
-    // view_block: screen-space backward only -- the render-gradient sums, flags and camera go
-    // into the block (gsr_rasterize_backward_screen) and the per-Gaussian backward is skipped
+    if (int rc = check_struct("rasterize_backward", args, args ? args->struct_size : 0, sizeof(gsr_backward_args)))
+        return rc;
+    const gsr_scene& scene = args->scene;
+    const gsr_view& view = args->view;
+    const int P = scene.P, D = scene.D, R = args->R, width = view.width, height = view.height;
+    const float *means3D = scene.means3D, *dc = scene.dc, *shs = scene.shs, *colors_precomp = scene.colors_precomp,
+                *opacities = scene.opacities, *scales = scene.scales, *rotations = scene.rotations,
+                *cov3D_precomp = scene.cov3D_precomp;
+    const float scale_modifier = scene.scale_modifier, tan_fovx = view.tan_fovx, tan_fovy = view.tan_fovy;
+    const float *background = view.background, *viewmatrix = view.viewmatrix, *projmatrix = view.projmatrix,
+                *campos = view.campos;
+    const int antialiasing = view.antialiasing, debug = args->debug, binning_capacity = args->binning_capacity;
+    const size_t binning_bytes = args->binning_bytes;
+    const int* radii = args->radii;
+    void *const geom_buffer = args->geom_buffer, *const binning_buffer = args->binning_buffer,
+                *const image_buffer = args->image_buffer;
+    const float *dL_dpix = args->dL_dpix, *dL_dinvdepths = args->dL_dinvdepths, *dL_dalphas = args->dL_dalphas;
+    float *const dL_dmean2D = args->dL_dmean2D, *const dL_dmean2D_abs = args->dL_dmean2D_abs,
+                 *const dL_dconic = args->dL_dconic, *const dL_dopacity = args->dL_dopacity,
+                 *const dL_dcolor = args->dL_dcolor, *const dL_dinvdepth = args->dL_dinvdepth,
+                 *const dL_dmean3D = args->dL_dmean3D, *const dL_dcov3D = args->dL_dcov3D,
+                 *const dL_ddc = args->dL_ddc, *const dL_dsh = args->dL_dsh, *const dL_dscale = args->dL_dscale,
+                 *const dL_drot = args->dL_drot, *const view_block = args->view_block;
+    const gsr_alloc_fn scratch_alloc = args->scratch_alloc;
+    void* const scratch_ctx = args->scratch_ctx;
+    hipStream_t stream = (hipStream_t)args->stream;
+    // view_block: screen-space backward only -- the render-gradient sums, flags and camera go into the block
+    // (the multi-GPU view exchange) and the per-Gaussian backward, with its outputs, is skipped
     const bool screen = view_block != nullptr;
+    if (screen) {
+        if ((reinterpret_cast<uintptr_t>(view_block) & 15) != 0)
+            return fail(GSR_ERR_ARGUMENT, "rasterize_backward_screen: view block must be 16-byte aligned");
+        if (colors_precomp || cov3D_precomp)  // (per view: the exchange's per-Gaussian backward has neither)
+            return fail(GSR_ERR_ARGUMENT, "rasterize_backward_screen: precomputed colours / cov3D with a view block");
+    }
     if (P < 0 || R < 0 || width <= 0 || height <= 0)
         return fail(GSR_ERR_ARGUMENT, "rasterize_backward: invalid sizes P=%d R=%d W=%d H=%d", P, R, width, height);
     if (P == 0) return GSR_OK;
@@ -983,12 +998,13 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
         if ((dL_dinvdepths == nullptr) != (dL_dinvdepth == nullptr))
             return fail(GSR_ERR_ARGUMENT, "rasterize_backward: dL_dinvdepths and dL_dinvdepth go together");
     }
-    if (dc && M > 0 && !shs) return fail(GSR_ERR_ARGUMENT, "rasterize_backward: %d rest SH coefficients but no shs", M);
+    if (dc && scene.M > 0 && !shs)
+        return fail(GSR_ERR_ARGUMENT, "rasterize_backward: %d rest SH coefficients but no shs", scene.M);
     if (dL_dmean2D_abs && screen)
         return fail(GSR_ERR_ARGUMENT, "rasterize_backward: the view-block backward has no absolute gradient");
     if (dL_dmean2D_abs && g_census)  // (render_bwd has no CENSUS x ABSGRAD instantiation)
         return fail(GSR_ERR_ARGUMENT, "rasterize_backward: dL_dmean2D_abs cannot be combined with the census");
-    if (dc) M += 1;  // as in the forward
+    const int M = dc ? scene.M + 1 : scene.M;  // as in the forward
     if (!colors_precomp && (shs || dc) && (D < 0 || D > 3 || (D + 1) * (D + 1) > M))
         return fail(GSR_ERR_ARGUMENT, "rasterize_backward: SH degree %d needs %d coefficients, got %d", D,
                     (D + 1) * (D + 1), M);
@@ -1193,80 +1209,7 @@ int backward_impl(int P, int D, int M, int R, const float* background, int width
 }
 }  // namespace
 
-int gsr_rasterize_backward(int P, int D, int M, int R, const float* background, int width, int height,
-                           const float* means3D, const float* shs, const float* colors_precomp,
-                           const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                           const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                           void* binning_buffer, void* image_buffer, const float* dL_dpix, const float* dL_dinvdepths,
-                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                           float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                           float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                           void* scratch_ctx, void* stream) {
-    return backward_impl(P, D, M, R, background, width, height, means3D, nullptr, shs, colors_precomp, opacities, scales,
-                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, nullptr, dL_dsh, dL_dscale,
-                         dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream, 0, 0);
-}
-
-int gsr_rasterize_backward_ex(int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp,
-                              const float* opacities, const float* scales, float scale_modifier,
-                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
-                              const float* dL_dpix, const float* dL_dinvdepths, float* dL_dmean2D, float* dL_dconic,
-                              float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D,
-                              float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing,
-                              int debug, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream,
-                              int binning_capacity, size_t binning_bytes) {
-    return backward_impl(P, D, M, R, background, width, height, means3D, nullptr, shs, colors_precomp, opacities, scales,
-                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, nullptr, dL_dsh, dL_dscale,
-                         dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream, binning_capacity,
-                         binning_bytes);
-}
-
-int gsr_rasterize_forward_dc(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                             gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
-                             int width, int height, const float* means3D, const float* dc, const float* shs,
-                             const float* colors_precomp, const float* opacities, const float* scales,
-                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                             const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                             float tan_fovy, int prefiltered, float* out_color, float* out_invdepth, int antialiasing,
-                             int* radii, int debug, void* stream, int* num_rendered, int capacity_hint,
-                             int* binning_capacity) {
-    if (!dc && !colors_precomp)
-        return fail(GSR_ERR_ARGUMENT, "rasterize_forward_dc: provide dc (+ shs) or precomputed colours");
-    return forward_impl(geom_alloc, geom_ctx, binning_alloc, binning_ctx, image_alloc, image_ctx, P, D, M, background,
-                        width, height, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                        cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
-                        out_invdepth, antialiasing, radii, debug, stream, num_rendered, capacity_hint,
-                        binning_capacity);
-}
-
-int gsr_rasterize_backward_dc(int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                              const float* opacities, const float* scales, float scale_modifier,
-                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
-                              const float* dL_dpix, const float* dL_dinvdepths, float* dL_dmean2D, float* dL_dconic,
-                              float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D,
-                              float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                              int antialiasing, int debug, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
-                              void* stream, int binning_capacity, size_t binning_bytes) {
-    if (!dc && !colors_precomp)
-        return fail(GSR_ERR_ARGUMENT, "rasterize_backward_dc: provide dc (+ shs) or precomputed colours");
-    return backward_impl(P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
-                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh,
-                         dL_dscale, dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream,
-                         binning_capacity, binning_bytes);
-}
+int gsr_rasterize_backward(const gsr_backward_args* args) { return backward_impl(args); }
 
 int gsr_render_alpha(int width, int height, const void* image_buffer, float* out_alpha, void* stream) {
     using namespace gsr;
@@ -1471,68 +1414,6 @@ int gsr_render_features_backward(int P, int C, int R, int width, int height, con
 
 int gsr_render_features_chunk(void) { return gsr::kFeatChunk; }
 
-int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
-                                 const float* means3D, const float* dc, const float* shs,
-                                 const float* colors_precomp, const float* opacities, const float* scales,
-                                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                                 const float* viewmatrix, const float* projmatrix, const float* campos,
-                                 float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                                 void* binning_buffer, void* image_buffer, const float* dL_dpix,
-                                 const float* dL_dinvdepths, const float* dL_dalphas, float* dL_dmean2D,
-                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth,
-                                 float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
-                                 float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                                 void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes) {
-    // (dc == NULL: the combined layout, shs holding every coefficient; dL_ddc is then not written)
-    return backward_impl(P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
-                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, dc ? dL_ddc : nullptr,
-                         dL_dsh, dL_dscale, dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream,
-                         binning_capacity, binning_bytes, dL_dalphas);
-}
-
-int gsr_rasterize_backward_abs(int P, int D, int M, int R, const float* background, int width, int height,
-                               const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                               const float* opacities, const float* scales, float scale_modifier,
-                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                               const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                               const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
-                               const float* dL_dpix, const float* dL_dinvdepths, const float* dL_dalphas,
-                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                               float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
-                               float* dL_dscale, float* dL_drot, int antialiasing, int debug,
-                               gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream, int binning_capacity,
-                               size_t binning_bytes, float* dL_dmean2D_abs) {
-    return backward_impl(P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
-                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
-                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, dL_dmean2D,
-                         dL_dconic, dL_dopacity, dL_dcolor, dL_dinvdepth, dL_dmean3D, dL_dcov3D, dc ? dL_ddc : nullptr,
-                         dL_dsh, dL_dscale, dL_drot, antialiasing, debug, scratch_alloc, scratch_ctx, stream,
-                         binning_capacity, binning_bytes, dL_dalphas, nullptr, dL_dmean2D_abs);
-}
-
-}  // extern "C"
-
-int gsr_rasterize_backward_screen(int P, int D, int M, int R, const float* background, int width, int height,
-                                  const float* means3D, const float* dc, const float* shs, const float* opacities,
-                                  const float* scales, float scale_modifier, const float* rotations,
-                                  const float* viewmatrix, const float* projmatrix, const float* campos,
-                                  float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                                  void* binning_buffer, void* image_buffer, const float* dL_dpix,
-                                  const float* dL_dinvdepths, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                                  void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes,
-                                  float* view_block) {
-    if (!view_block) return fail(GSR_ERR_ARGUMENT, "rasterize_backward_screen: null view block");
-    if ((reinterpret_cast<uintptr_t>(view_block) & 15) != 0)
-        return fail(GSR_ERR_ARGUMENT, "rasterize_backward_screen: view block must be 16-byte aligned");
-    return backward_impl(P, D, M, R, background, width, height, means3D, dc, shs, nullptr, opacities, scales,
-                         scale_modifier, rotations, nullptr, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                         geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dinvdepths, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, antialiasing, debug,
-                         scratch_alloc, scratch_ctx, stream, binning_capacity, binning_bytes, nullptr, view_block);
-}
-
 int gsr_debug_forward_state(int P, int width, int height, int R, int binning_capacity, size_t binning_bytes,
                             const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                             unsigned int* ranges, unsigned int* point_list, unsigned int* n_contrib, float* final_T,
@@ -1608,3 +1489,5 @@ int gsr_debug_near_state(int P, int width, int height, const void* geom_buffer, 
                 "debug_near_state sranges");
     return GSR_OK;
 }
+
+}  // extern "C"

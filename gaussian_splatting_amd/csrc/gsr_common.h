@@ -206,7 +206,7 @@ __host__ __device__ inline uint32_t unit_part_cap(uint32_t tiles) { return (tile
 __host__ __device__ inline size_t unit_full_cap(size_t C) { return C / kCkStride + 1; }
 
 // ---------------------------------------------------------------------------
-// View block (multi-GPU exchange, include/gsr.h gsr_rasterize_backward_screen /
+// View block (multi-GPU exchange, include/gsr.h gsr_backward_args.view_block /
 // gsr_gauss_backward_views): one view's camera and per-Gaussian render-gradient sums,
 // in floats: [0, 64) header (the camera, offsets below), then sums.a [P][4], sums.b [P][4],
 // sums.c [P][2] and the flag word [P] (bit 0 visible, bits 1-3 SH clamp mask); the block

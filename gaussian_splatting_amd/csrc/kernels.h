@@ -114,7 +114,7 @@ struct RenderBwdArgs {
     // seed of the per-pixel scalar gB beside the background term, whose form it shares (non-null selects
     // render_bwd's ALPHA instantiations; the others never read it)
     const float* dL_dalpha;
-    // absolute screen-space gradient (gsr_rasterize_backward_abs): non-zero selects render_bwd's ABSGRAD
+    // absolute screen-space gradient (gsr_backward_args.dL_dmean2D_abs): non-zero selects render_bwd's ABSGRAD
     // instantiations, which also sum each entry's per-pixel |dL/dmean2D| terms -- into floats 10, 11 of the
     // accumulator row (atomic), or the record's two pad floats.  Not with the census.
     int absgrad;

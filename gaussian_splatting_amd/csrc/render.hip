@@ -523,7 +523,7 @@ hipError_t launch_render_fwd(const RenderFwdArgs& a, hipStream_t stream, int qua
 // |k x| = |k| |x|, so the per-pixel factor is the staged conic alone and the flush applies W o / log2e (H o / log2e)
 // once per entry.  They are folded like r8 / r9 into a fourth plane of s_acc (row partials), land behind dconic
 // in the entry's final form -- accumulator row floats 10, 11 (zero otherwise), the record's two pad floats -- and
-// gauss_bwd / gauss_reduce turn them into the [P,3] output (include/gsr.h gsr_rasterize_backward_abs).  With
+// gauss_bwd / gauss_reduce turn them into the [P,3] output (include/gsr.h dL_dmean2D_abs).  With
 // ABSGRAD false the generated code is that of the kernel without the feature.
 template <bool CENSUS, bool STRIDED, bool ATOMIC, bool ALPHA, bool ABSGRAD = false>
 __global__ void __launch_bounds__(64) render_bwd_kernel(RenderBwdArgs a) {

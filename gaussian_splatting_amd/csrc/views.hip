@@ -40,7 +40,7 @@ struct ViewsBwdArgs {
 };
 
 // ---- 1. a view block from a screen-space backward ---------------------------------
-// The atomic backward into a view block (gsr_rasterize_backward_screen, multi-GPU view exchange): one lane
+// The atomic backward into a view block (gsr_backward_args.view_block, multi-GPU view exchange): one lane
 // per Gaussian writes its dense sums -- its accumulator row if its touched bit is set (the row then zeroed),
 // zeros otherwise -- and its flag word, as gauss_reduce does for a view block; the words it read are cleared.
 __global__ void __launch_bounds__(64) gauss_live_views_kernel(int P, uint32_t* __restrict__ touched,

@@ -136,7 +136,7 @@ def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib
 
     ``absgrad=True`` (an extension, gsplat's convention): the backward of this render also sets
     ``means2D.absgrad`` [P,3] (float32, on the device): per Gaussian the sum over pixels of the ABSOLUTE value of
-    each pixel's term of ``means2D.grad`` (AbsGS; include/gsr.h gsr_rasterize_backward_abs), column 2 zero.  Each
+    each pixel's term of ``means2D.grad`` (AbsGS; include/gsr.h gsr_backward_args.dL_dmean2D_abs), column 2 zero.  Each
     backward overwrites it.  Without the keyword no attribute is set and nothing more is launched or allocated.
 
     ``return_contrib=True`` (an extension): one more output, LAST (after ``alpha`` when both are asked for): the

@@ -29,8 +29,8 @@
  *    (rasterize_points.cu:29-43); their contents are private to this library and
  *    must be passed back unchanged to gsr_rasterize_backward;
  *  - all work is enqueued on `stream` (a hipStream_t; NULL = the default stream).
- *    gsr_rasterize_forward synchronises that stream once, to learn the number of
- *    tile instances (cuda_rasterizer/rasterizer_impl.cu:313).
+ *    gsr_rasterize_forward waits on it once, to learn the number of tile instances
+ *    (cuda_rasterizer/rasterizer_impl.cu:313; see gsr_forward_args.capacity_hint).
  *
  * Every function returns 0 on success or a nonzero GSR_ERR_* code; the message
  * of the last failure on the calling thread is available from gsr_last_error().
@@ -56,109 +56,160 @@ extern "C" {
  * Replaces std::function<char*(size_t)> (rasterize_points.cu:29-43). */
 typedef void* (*gsr_alloc_fn)(void* ctx, size_t nbytes);
 
-/* Forward pass (CudaRasterizer::Rasterizer::forward).
- * P Gaussians, active SH degree D, M SH coefficients per Gaussian (0 if shs is NULL).
- * out_color [3,H,W], out_invdepth [1,H,W] and radii [P] are written for every
- * element.  *num_rendered receives the number of (tile, Gaussian) instances. */
-int gsr_rasterize_forward(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                          gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
-                          int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
-                          const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                          const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
-                          float* out_invdepth, int antialiasing, int* radii, int debug, void* stream,
-                          int* num_rendered);
+/* Argument structs.  gsr_rasterize_forward and gsr_rasterize_backward each take one struct; the Gaussians
+ * (gsr_scene) and the camera (gsr_view) are grouped, because both passes read them.  A caller zero-initialises
+ * the struct, sets struct_size to its sizeof and assigns the fields it uses by name: an optional pointer left
+ * NULL selects the call without it, as documented on the field.  A struct_size other than the library's own
+ * sizeof is GSR_ERR_ARGUMENT (the message names both sizes), checked before any other field is read. */
 
-/* Same as gsr_rasterize_forward, without the mid-forward host synchronisation.
- * The binning buffer is requested for capacity_hint instances before the count is
- * known (typically the previous call's num_rendered plus a margin), the tile sort
- * runs on that capacity with the unused slots padded, and the stream is
- * synchronised once at the end to read num_rendered.  If num_rendered exceeds the
- * hint, the binning stage is redone exactly (the binning callback is called again
- * with a larger size).  capacity_hint <= 0 behaves like gsr_rasterize_forward.
- * *binning_capacity receives the capacity the binning buffer was laid out for;
- * pass it to gsr_rasterize_backward_ex. */
-int gsr_rasterize_forward_ex(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                             gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
-                             int width, int height, const float* means3D, const float* shs,
-                             const float* colors_precomp, const float* opacities, const float* scales,
-                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                             const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                             float tan_fovy, int prefiltered, float* out_color, float* out_invdepth, int antialiasing,
-                             int* radii, int debug, void* stream, int* num_rendered, int capacity_hint,
-                             int* binning_capacity);
+/* The Gaussians: what the forward renders and the backward differentiates. */
+typedef struct gsr_scene {
+    int P; /* Gaussians */
+    int D; /* active SH degree, 0..3; (D + 1)^2 coefficients must be present.  Ignored with colors_precomp */
+    int M; /* SH coefficients per Gaussian in shs: all of them (dc NULL) or the REST (dc given; 15 at
+              degree 3).  0 if shs is NULL */
+    const float* means3D; /* [P,3] */
+    /* Separate-DC layout: the 3DGS-accel rasterizer's interface (the build that ships SparseGaussianAdam), which
+     * the reference's callers select with separate_sh=True (train.py:41-45,105,144;
+     * gaussian_renderer/__init__.py:106-125 passes dc= and shs= = GaussianModel._features_dc / _features_rest).
+     * dc [P,1,3] is coefficient 0; the colour is the same polynomial as with one combined [P,M+1,3] array.
+     * NULL: the combined layout, shs holding all M coefficients; dL_ddc is then not written. */
+    const float* dc;
+    const float* shs;            /* [P,M,3]; NULL with colors_precomp, or with dc when M == 0 */
+    const float* colors_precomp; /* [P,3] or NULL: colours from SH (then dc or shs, and view.campos, are required) */
+    const float* opacities;      /* [P] */
+    const float* scales;         /* [P,3]; NULL with cov3D_precomp */
+    float scale_modifier;
+    const float* rotations;     /* [P,4]; NULL with cov3D_precomp */
+    const float* cov3D_precomp; /* [P,6] or NULL: covariance from scales and rotations */
+} gsr_scene;
 
-/* Backward pass (CudaRasterizer::Rasterizer::backward).
- * R = num_rendered from the forward; geom/binning/image buffers are the ones the
- * forward's callbacks returned.  dL_dinvdepths ([1,H,W]) may be NULL, in which
- * case dL_dinvdepth must be NULL too.  dL_dconic ([P,4]) may be NULL.  Every
- * element of every non-NULL output is written (no pre-zeroing needed).
- * `scratch_alloc` provides 48 bytes per tile instance for the per-instance
- * gradient records, plus 40 bytes and a live-list slot per Gaussian.  The backward
- * also sets the records' content bytes, which live in the forward's binning buffer
- * (zeroed by the forward); they depend on the geometry only, so a second backward of
- * the same forward (retain_graph) sets the same bytes. */
-int gsr_rasterize_backward(int P, int D, int M, int R, const float* background, int width, int height,
-                           const float* means3D, const float* shs, const float* colors_precomp,
-                           const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                           const float* campos, float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                           void* binning_buffer, void* image_buffer, const float* dL_dpix, const float* dL_dinvdepths,
-                           float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                           float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
-                           float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                           void* scratch_ctx, void* stream);
+/* The camera and the image. */
+typedef struct gsr_view {
+    int width, height;
+    const float* background; /* [3] */
+    const float* viewmatrix; /* [16], read column-major */
+    const float* projmatrix; /* [16], read column-major */
+    const float* campos;     /* [3]; the forward needs it for SH colours only (NULL with colors_precomp), the
+                                backward always */
+    float tan_fovx, tan_fovy;
+    int antialiasing;
+} gsr_view;
 
-/* Backward for a forward made by gsr_rasterize_forward_ex: binning_capacity is the
- * value it returned, or 0.  With 0 and a nonzero binning_bytes (the binning buffer's
- * size) the capacity is recovered from the size: gsr_rasterize_forward_ex lays the
- * buffer out for a multiple of 256 instances, over which the size determines the layout
- * (so the buffer can travel through any tensor copy, e.g. saved-tensor hooks).  With 0
- * and 0 it is R (gsr_rasterize_forward's exact layout).  A size that matches no layout,
- * or a given capacity whose layout has another size, is GSR_ERR_ARGUMENT. */
-int gsr_rasterize_backward_ex(int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp,
-                              const float* opacities, const float* scales, float scale_modifier,
-                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
-                              const float* dL_dpix, const float* dL_dinvdepths, float* dL_dmean2D, float* dL_dconic,
-                              float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D,
-                              float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing,
-                              int debug, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream,
-                              int binning_capacity, size_t binning_bytes);
+/* Forward pass (CudaRasterizer::Rasterizer::forward).  out_color, out_invdepth and radii are written for every
+ * element.  With P == 0 nothing is launched or allocated and the two results are 0. */
+typedef struct gsr_forward_args {
+    size_t struct_size; /* sizeof(gsr_forward_args) */
+    gsr_scene scene;
+    gsr_view view;
+    /* the three scratch buffers (see "Conventions" above); pass them back unchanged to the backward */
+    gsr_alloc_fn geom_alloc;
+    void* geom_ctx;
+    gsr_alloc_fn binning_alloc; /* called again, with a larger size, when capacity_hint was too small */
+    void* binning_ctx;
+    gsr_alloc_fn image_alloc;
+    void* image_ctx;
+    int prefiltered; /* != 0: GSR_ERR_PREFILTERED if a point fails the frustum test */
+    int debug;       /* != 0: synchronise and check for errors after every stage */
+    void* stream;
+    float* out_color;    /* [3,H,W] */
+    float* out_invdepth; /* [1,H,W] */
+    int* radii;          /* [P] */
+    /* > 0: no mid-forward host synchronisation.  The binning buffer is requested for capacity_hint instances
+     * before the count is known (typically the previous call's num_rendered plus a margin), the tile sort runs
+     * on that capacity with the unused slots padded, and the host waits once, for the instance count only.  If
+     * num_rendered exceeds the hint, the binning stage is redone exactly (gsr_forward_rebuilds counts these).
+     * <= 0: the reference's synchronising forward -- the count is read back (CR/rasterizer_impl.cu:313) before
+     * the binning buffer is requested. */
+    int capacity_hint;
+    /* results, written by the call */
+    int num_rendered; /* (tile, Gaussian) instances: the backward's R */
+    /* The capacity the binning buffer was laid out for: num_rendered or capacity_hint, whichever is larger,
+     * rounded up to a multiple of 256 instances -- over which the buffer's size determines the layout, so the
+     * backward can take binning_bytes instead of this value.  Only a capacity whose rounding would pass INT_MAX
+     * is kept exact (C = num_rendered); the backward still recovers that layout from the buffer's size. */
+    int binning_capacity;
+} gsr_forward_args;
 
-/* Separate-DC variants: the 3DGS-accel rasterizer's interface (the build that ships
- * SparseGaussianAdam), which the reference's callers select with separate_sh=True
- * (train.py:41-45,105,144; gaussian_renderer/__init__.py:106-125 passes dc= and
- * shs= = GaussianModel._features_dc / _features_rest).  Its _C.rasterize_gaussians /
- * _C.rasterize_gaussians_backward take `dc` right before `sh`, and the backward returns
- * dL_ddc before dL_dsh.  Here: dc is [P,1,3] (coefficient 0), shs is [P,M,3] with M
- * the number of REST coefficients (15 at SH degree 3; shs may be NULL when M == 0), and
- * the colour is the same polynomial as with one combined [P,M+1,3] array.  dL_ddc
- * ([P,1,3]) and dL_dsh ([P,M,3]) are written for every element.  Everything else is
- * gsr_rasterize_forward_ex / gsr_rasterize_backward_ex. */
-int gsr_rasterize_forward_dc(gsr_alloc_fn geom_alloc, void* geom_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
-                             gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background,
-                             int width, int height, const float* means3D, const float* dc, const float* shs,
-                             const float* colors_precomp, const float* opacities, const float* scales,
-                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                             const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
-                             float tan_fovy, int prefiltered, float* out_color, float* out_invdepth, int antialiasing,
-                             int* radii, int debug, void* stream, int* num_rendered, int capacity_hint,
-                             int* binning_capacity);
+/* Backward pass (CudaRasterizer::Rasterizer::backward), of the forward that filled the three buffers, with that
+ * forward's scene and view.  Every element of every non-NULL output is written (no pre-zeroing needed).  The
+ * backward also sets the gradient records' content bytes, which live in the forward's binning buffer (zeroed
+ * by the forward); they depend on the geometry only, so a second backward of the same forward (retain_graph)
+ * sets the same bytes.  With P == 0 nothing is launched. */
+typedef struct gsr_backward_args {
+    size_t struct_size; /* sizeof(gsr_backward_args) */
+    gsr_scene scene;
+    gsr_view view;
+    int R;            /* the forward's num_rendered */
+    const int* radii; /* [P], as the forward wrote them */
+    void* geom_buffer;
+    void* binning_buffer; /* may be NULL when R == 0 */
+    void* image_buffer;
+    /* The binning buffer's layout: binning_capacity is the value the forward returned, or 0.  With 0 and a
+     * nonzero binning_bytes (the buffer's size) the capacity is recovered from the size: the forward lays the
+     * buffer out for a multiple of 256 instances, over which the size determines the layout (so the buffer can
+     * travel through any tensor copy, e.g. saved-tensor hooks), or, for a capacity above INT_MAX - 255, exactly
+     * for R, which the size identifies too.  With 0 and 0 the layout is the exact one for R.  A size that
+     * matches no layout, or a given capacity whose layout has another size, is GSR_ERR_ARGUMENT. */
+    int binning_capacity;
+    size_t binning_bytes;
+    /* upstream gradients */
+    const float* dL_dpix;       /* [3,H,W] */
+    const float* dL_dinvdepths; /* [1,H,W] or NULL: no inverse-depth loss; dL_dinvdepth must then be NULL too */
+    /* [1,H,W] or NULL (then exactly the call without it): the gradient of the accumulated alpha A
+     * (gsr_render_alpha).  dA/dalpha_i = +final_T / (1 - alpha_i) has the form of the colour's background term
+     * (CR/backward.cu:587-590) with -1 in place of bg . dL_dpix, and enters the blend backward there; the
+     * conventions are the colour's (no gradient through the early termination, the skip tests or the 0.99
+     * clamp).  Every output carries the alpha loss's share except dL_dcolor / dL_dsh / dL_ddc / dL_dinvdepth,
+     * which it does not reach.  gsr_camera_backward, run on the outputs, gives the camera gradients of the alpha
+     * loss too (campos gets none: A does not depend on the colours).  Not supported yet: a gradient for the
+     * background. */
+    const float* dL_dalphas;
+    /* outputs */
+    float* dL_dmean2D; /* [P,3] */
+    /* [P,3] or NULL (then exactly the call without it): the absolute screen-space gradient, the densification
+     * statistic of AbsGS (gsplat's absgrad).  dL_dmean2D is a signed sum over pixels, so the per-pixel terms of
+     * a large Gaussian cancel across its centre; the absolute value has to be taken per pixel, inside the render
+     * backward.  For Gaussian g
+     *     dL_dmean2D_abs[g] = (sum_pix |t_x(g, pix)|, sum_pix |t_y(g, pix)|, 0),
+     * t_x, t_y the terms the reference adds per pixel into dL_dmean2D (CR/backward.cu:600-601), in the same NDC
+     * units (x 0.5 W, 0.5 H).  A pixel's term is its total over all upstream maps (colour, inverse depth and,
+     * when given, alpha), the sum runs over every tile instance of the Gaussian, and the skip tests, early
+     * termination, 0.99 clamp and antialiasing are those of dL_dmean2D.  Every element is written; rows with
+     * radii == 0 are zero, and R == 0 gives zeros.  Every other output is what the call without it writes
+     * (bitwise on the record path, "bwd_atomic" 0, where dL_dmean2D_abs is bitwise reproducible too).
+     * GSR_ERR_ARGUMENT when the census is set (gsr_census_set): the census form of the render backward has no
+     * absolute-gradient variant; and with view_block: view blocks carry no absolute gradient. */
+    float* dL_dmean2D_abs;
+    float* dL_dconic;    /* [P,4] or NULL: not stored (gsr_camera_backward reads it) */
+    float* dL_dopacity;  /* [P] */
+    float* dL_dcolor;    /* [P,3] */
+    float* dL_dinvdepth; /* [P] or NULL, together with dL_dinvdepths */
+    float* dL_dmean3D;   /* [P,3] */
+    float* dL_dcov3D;    /* [P,6] */
+    float* dL_ddc;       /* [P,1,3]; required with scene.dc (and SH colours), not written without it */
+    float* dL_dsh;       /* [P,M,3]; required with scene.shs (and SH colours) */
+    float* dL_dscale;    /* [P,3]; required with scene.scales, as dL_drot */
+    float* dL_drot;      /* [P,4] */
+    /* NULL: the whole backward, into the outputs above.  Non-NULL (device, 16-byte aligned,
+     * gsr_view_block_floats(P) floats): the screen-space backward of the multi-GPU view exchange (below) -- the
+     * backward up to the per-Gaussian sums (CR/backward.cu:433-612 = renderCUDA backward), written with the
+     * camera into the block; the per-Gaussian backward is left to gsr_gauss_backward_views and the outputs above
+     * are ignored.  Colours come from SH (dc + shs, or shs alone) and cov3D from scales / rotations:
+     * colors_precomp or cov3D_precomp with a view block is GSR_ERR_ARGUMENT, as is dL_dmean2D_abs.  Not
+     * covered: an alpha loss over view blocks (the view exchange sets no dL_dalphas).  dL/dmeans2D of this view
+     * is the block's float pair at [64 + 4P + 2g] (densification). */
+    float* view_block;
+    int debug; /* != 0: synchronise and check for errors after every stage */
+    /* 48 bytes per tile instance for the per-instance gradient records, plus 40 bytes and a live-list slot per
+     * Gaussian */
+    gsr_alloc_fn scratch_alloc;
+    void* scratch_ctx;
+    void* stream;
+} gsr_backward_args;
 
-int gsr_rasterize_backward_dc(int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                              const float* opacities, const float* scales, float scale_modifier,
-                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                              const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
-                              const float* dL_dpix, const float* dL_dinvdepths, float* dL_dmean2D, float* dL_dconic,
-                              float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D,
-                              float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                              int antialiasing, int debug, gsr_alloc_fn scratch_alloc, void* scratch_ctx,
-                              void* stream, int binning_capacity, size_t binning_bytes);
+int gsr_rasterize_forward(gsr_forward_args* args);
+int gsr_rasterize_backward(const gsr_backward_args* args);
 
 /* Accumulated alpha (silhouette): a third differentiable map beside colour and inverse depth,
  * A[pix] = 1 - final_T[pix], final_T the transmittance after the pixel's last contributor -- the
@@ -166,64 +217,11 @@ int gsr_rasterize_backward_dc(int P, int D, int M, int R, const float* backgroun
  * A == 0.0 exactly.  No reference counterpart; the forward keeps final_T in its image buffer anyway.
  *
  * gsr_render_alpha: writes A ([1,H,W], row-major, every element) from the image buffer of a finished
- *   forward of the same width and height (any of the three), one small kernel on `stream`; call it after
- *   the forward, on the forward's stream or one ordered behind it.  Valid only for P > 0 (a forward of no
- *   Gaussians allocates no image buffer: A is then all zeros).  GSR_ERR_ARGUMENT on non-positive sizes or
- *   a NULL pointer.
- * gsr_rasterize_backward_alpha: gsr_rasterize_backward_dc with an upstream gradient dL_dalphas ([1,H,W],
- *   may be NULL: then exactly gsr_rasterize_backward_dc) of A.  dA/dalpha_i = +final_T / (1 - alpha_i) has
- *   the form of the colour's background term (CR/backward.cu:587-590) with -1 in place of bg . dL_dpix, and
- *   enters the blend backward there; the conventions are the colour's (no gradient through the early
- *   termination, the skip tests or the 0.99 clamp).  Every output carries the alpha loss's share except
- *   dL_dcolor / dL_dsh / dL_ddc / dL_dinvdepth, which it does not reach.  Unlike _dc, dc may be NULL: shs is
- *   then the combined [P,M,3] array as in gsr_rasterize_backward_ex and dL_ddc is not written (what
- *   gsr_rasterize_backward_screen accepts).  gsr_camera_backward, run on the outputs, gives the camera
- *   gradients of the alpha loss too (campos gets none: A does not depend on the colours).  Not supported
- *   yet: the multi-GPU view blocks (gsr_rasterize_backward_screen takes no dL_dalphas) and a gradient
- *   for the background. */
+ *   forward of the same width and height, one small kernel on `stream`; call it after the forward, on the
+ *   forward's stream or one ordered behind it.  Valid only for P > 0 (a forward of no Gaussians allocates no
+ *   image buffer: A is then all zeros).  GSR_ERR_ARGUMENT on non-positive sizes or a NULL pointer.
+ * Its gradient enters the backward as gsr_backward_args.dL_dalphas. */
 int gsr_render_alpha(int width, int height, const void* image_buffer, float* out_alpha, void* stream);
-
-int gsr_rasterize_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
-                                 const float* means3D, const float* dc, const float* shs,
-                                 const float* colors_precomp, const float* opacities, const float* scales,
-                                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                                 const float* viewmatrix, const float* projmatrix, const float* campos,
-                                 float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                                 void* binning_buffer, void* image_buffer, const float* dL_dpix,
-                                 const float* dL_dinvdepths, const float* dL_dalphas, float* dL_dmean2D,
-                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth,
-                                 float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
-                                 float* dL_drot, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                                 void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes);
-
-/* Absolute screen-space gradient (the densification statistic of AbsGS; gsplat's absgrad).
- * dL_dmean2D is a signed sum over pixels, so the per-pixel terms of a large Gaussian cancel across its
- * centre; the absolute value has to be taken per pixel, inside the render backward.
- *
- * gsr_rasterize_backward_abs: gsr_rasterize_backward_alpha with one more output dL_dmean2D_abs ([P,3], may
- *   be NULL: then exactly gsr_rasterize_backward_alpha).  For Gaussian g
- *     dL_dmean2D_abs[g] = (sum_pix |t_x(g, pix)|, sum_pix |t_y(g, pix)|, 0),
- *   t_x, t_y the terms the reference adds per pixel into dL_dmean2D (CR/backward.cu:600-601), in the same
- *   NDC units (x 0.5 W, 0.5 H).  A pixel's term is its total over all upstream maps (colour, inverse depth
- *   and, when given, alpha), the sum runs over every tile instance of the Gaussian, and the skip tests, early
- *   termination, 0.99 clamp and antialiasing are those of dL_dmean2D.  Every element is written; rows with
- *   radii == 0 are zero, and P == 0 or R == 0 gives zeros.  Every other output is what
- *   gsr_rasterize_backward_alpha writes (bitwise on the record path, "bwd_atomic" 0, where dL_dmean2D_abs is
- *   bitwise reproducible too).  GSR_ERR_ARGUMENT when the census is set (gsr_census_set): the census form
- *   of the render backward has no absolute-gradient variant.  Not supported: the multi-GPU view blocks
- *   (gsr_rasterize_backward_screen and the view exchange carry no absolute gradient). */
-int gsr_rasterize_backward_abs(int P, int D, int M, int R, const float* background, int width, int height,
-                               const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                               const float* opacities, const float* scales, float scale_modifier,
-                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                               const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
-                               const int* radii, void* geom_buffer, void* binning_buffer, void* image_buffer,
-                               const float* dL_dpix, const float* dL_dinvdepths, const float* dL_dalphas,
-                               float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                               float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
-                               float* dL_dscale, float* dL_drot, int antialiasing, int debug,
-                               gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream, int binning_capacity,
-                               size_t binning_bytes, float* dL_dmean2D_abs);
 
 /* Per-Gaussian contribution statistics (importance pruning: LightGaussian's global significance, RadSplat's
  * max-blend-weight pruning, visibility-count prunes).  The blend weight of Gaussian g at pixel pix is
@@ -232,9 +230,9 @@ int gsr_rasterize_backward_abs(int P, int D, int M, int R, const float* backgrou
  * before the pixel's termination -- the pairs the backward forms a gradient term for.  The maximum and the count
  * cannot be had from any backward (autograd only sees sums), so they are formed by a pass of their own.
  *
- * gsr_contrib_stats: from the three buffers of a finished forward (any of the three forwards, under every option,
- *   also one no backward will follow; P, R, width, height, binning_capacity / binning_bytes as
- *   gsr_rasterize_backward_ex takes them) into stats ([P,4], device, 16-byte aligned), row g =
+ * gsr_contrib_stats: from the three buffers of a finished forward (under every option, with or without a capacity
+ *   hint, also one no backward will follow; P, R, width, height, binning_capacity / binning_bytes as
+ *   gsr_backward_args takes them) into stats ([P,4], device, 16-byte aligned), row g =
  *     weight_sum    f32       sum of w over g's contributing pixels
  *     weight_max    f32       max of w over them
  *     pixel_count   u32 bits  their number
@@ -264,9 +262,9 @@ int gsr_contrib_stats(int P, int R, int width, int height, const void* geom_buff
  * A pass of its own over a finished forward's buffers instead of ceil(C/3) renders with colors_precomp, each of which
  * would repeat preprocess, binning and the sort.
  *
- * gsr_render_features: from the three buffers of a finished forward (any of the three forwards, under every option,
+ * gsr_render_features: from the three buffers of a finished forward (under every option, with or without a capacity hint,
  *   also one no backward will follow, and copies of the buffers; P, R, width, height, binning_capacity /
- *   binning_bytes as gsr_rasterize_backward_ex takes them) and features ([P,C], device) into out_features
+ *   binning_bytes as gsr_backward_args takes them) and features ([P,C], device) into out_features
  *   ([C,H,W], device), every element written; a pixel no Gaussian reaches is 0.0 exactly, and P == 0 or R == 0 gives
  *   zeros (the buffers may then be NULL).  The weights depend on the forward's discrete state alone (list order,
  *   blend masks, last contributors), each pixel is written by one wave and nothing is added atomically: the map is
@@ -318,27 +316,14 @@ int gsr_render_features_chunk(void);
  * over all views at once (10 (N-1) floats received per Gaussian instead of 118 (N-1)/N).
  *
  * gsr_view_block_floats(P): floats in one view block (padded to 256 B).
- * gsr_rasterize_backward_screen: the backward of gsr_rasterize_backward_dc up to the
- *   per-Gaussian sums (CR/backward.cu:433-612 = renderCUDA backward), written with the
- *   camera into view_block (device, 16-byte aligned, gsr_view_block_floats(P) floats);
- *   colours from SH (dc + shs, or shs alone with dc NULL), cov3D from scales/rotations.
- *   dL/dmeans2D of this view is the block's float pair at [64 + 4P + 2g] (densification).
+ * gsr_rasterize_backward with gsr_backward_args.view_block set: the screen-space backward, which
+ *   writes this rank's view block (documented on the field).
  * gsr_gauss_backward_views: the rest of the backward (CR/backward.cu:153-429,
- *   computeCov2DCUDA + preprocessCUDA, as gsr_rasterize_backward_dc's last stage) for all
+ *   computeCov2DCUDA + preprocessCUDA, as gsr_rasterize_backward's last stage) for all
  *   n_views gathered blocks (blocks[v * block_floats ...]), writing the SUM over views of
  *   dL/dmeans3D, dL/ddc, dL/dsh, dL/dopacity, dL/dscales, dL/drotations.  With one view it
  *   equals the single-view backward bit for bit. */
 unsigned long long gsr_view_block_floats(int P);
-
-int gsr_rasterize_backward_screen(int P, int D, int M, int R, const float* background, int width, int height,
-                                  const float* means3D, const float* dc, const float* shs, const float* opacities,
-                                  const float* scales, float scale_modifier, const float* rotations,
-                                  const float* viewmatrix, const float* projmatrix, const float* campos,
-                                  float tan_fovx, float tan_fovy, const int* radii, void* geom_buffer,
-                                  void* binning_buffer, void* image_buffer, const float* dL_dpix,
-                                  const float* dL_dinvdepths, int antialiasing, int debug, gsr_alloc_fn scratch_alloc,
-                                  void* scratch_ctx, void* stream, int binning_capacity, size_t binning_bytes,
-                                  float* view_block);
 
 int gsr_gauss_backward_views(int P, int D, int M, const float* means3D, const float* dc, const float* shs,
                              const float* opacities, const float* scales, const float* rotations, float scale_modifier,
@@ -410,7 +395,7 @@ int gsr_gauss_backward_views_live(int P, int D, int M, const float* means3D, con
                                   void* stream);
 
 /* Camera-pose gradients (no reference counterpart: the reference's rasterizer treats the camera as a
- * constant).  Run after gsr_rasterize_backward_ex / _dc of the same forward, on the same stream, with that
+ * constant).  Run after gsr_rasterize_backward of the same forward, on the same stream, with that
  * call's inputs and five of its per-Gaussian outputs: dL_dmean2D [P,3], dL_dconic [P,4] (which that call must
  * then be given; 16-byte aligned), dL_dopacity [P], dL_dcolor [P,3] and dL_dinvdepth [P] (NULL if the backward
  * had none).  Rows of Gaussians with radii == 0 are not read.  geom_buffer is the forward's geometry buffer
@@ -451,7 +436,7 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
  *                          entry = Gaussian index << 4 | the forward's 4-bit quadrant mask;
  *   n_contrib  [H*W]       last contributor (1-based list position) per pixel;
  *   final_T    [H*W]       transmittance after the last contributor.
- * binning_capacity / binning_bytes as for gsr_rasterize_backward_ex. */
+ * binning_capacity / binning_bytes as in gsr_backward_args. */
 int gsr_debug_forward_state(int P, int width, int height, int R, int binning_capacity, size_t binning_bytes,
                             const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                             unsigned int* ranges, unsigned int* point_list, unsigned int* n_contrib, float* final_T,
@@ -470,7 +455,7 @@ int gsr_debug_near_state(int P, int width, int height, const void* geom_buffer, 
                          unsigned int* near_ranges, void* stream);
 
 /* Number of forwards (process-wide) whose capacity hint was too small, so the binning stage
- * was redone with the exact count (gsr_rasterize_forward_ex). */
+ * was redone with the exact count (gsr_forward_args.capacity_hint). */
 long long gsr_forward_rebuilds(void);
 
 /* Host-side statistics since the last reset (reset != 0 clears after reading), for finding time

@@ -1,4 +1,4 @@
-"""Reference for the absolute screen-space gradient (AbsGS; include/gsr.h gsr_rasterize_backward_abs), built on
+"""Reference for the absolute screen-space gradient (AbsGS; include/gsr.h gsr_backward_args.dL_dmean2D_abs), built on
 the unchanged oracle.  TEST INFRASTRUCTURE ONLY (shared by tests/test_absgrad_ref.py and tests/test_gpu_absgrad.py).
 
     absgrad[g] = (sum_pix |t_x(g, pix)|, sum_pix |t_y(g, pix)|, 0)

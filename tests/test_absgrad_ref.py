@@ -58,15 +58,21 @@ def test_single_pixel_upstream_has_abs_equal_grad():
 
 
 def test_abi_declares_and_exports_the_absgrad_entry_point():
+    """include/gsr.h declares the absolute gradient as the output field dL_dmean2D_abs of gsr_rasterize_backward's
+    argument struct, _lib.BackwardArgs mirrors it (tests/test_abi_layout.py compares every field's offset and size
+    with the C compiler's), and a built library exports the function."""
+    import re
+
     from gaussian_splatting_amd import _lib
 
-    new = {"gsr_rasterize_backward_abs"}
+    new = {"gsr_rasterize_backward"}
     assert new <= set(_lib.header_symbols(_lib.HEADER_PATH))
     assert new <= set(_lib.SIGNATURES)
-    text = " ".join(open(_lib.HEADER_PATH).read().split())
-    assert "int binning_capacity, size_t binning_bytes, float* dL_dmean2D_abs);" in text
-    # the _alpha argument list plus the one output
-    assert len(_lib.SIGNATURES["gsr_rasterize_backward_abs"][1]) == len(_lib.SIGNATURES["gsr_rasterize_backward_alpha"][1]) + 1
+    text = open(_lib.HEADER_PATH).read()
+    struct = re.search(r"typedef struct gsr_backward_args \{(.*?)\} gsr_backward_args;", text, flags=re.S).group(1)
+    assert re.search(r"^\s*float\* dL_dmean2D_abs;", struct, flags=re.M)
+    assert "int gsr_rasterize_backward(const gsr_backward_args* args);" in text
+    assert "dL_dmean2D_abs" in dict(_lib.BackwardArgs._fields_)
     if os.path.exists(_lib.LIB_PATH):
         out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
         exported = {line.split()[-1] for line in out.splitlines() if line.strip()}

@@ -55,15 +55,22 @@ def test_alpha_gradient_constructions_agree(name):
 
 
 def test_abi_declares_and_exports_the_alpha_entry_points():
-    """(c) include/gsr.h declares gsr_render_alpha and gsr_rasterize_backward_alpha; a built library exports them."""
+    """(c) include/gsr.h declares gsr_render_alpha, and the alpha gradient as the field dL_dalphas of
+    gsr_rasterize_backward's argument struct (mirrored by _lib.BackwardArgs; tests/test_abi_layout.py holds the
+    two layouts together); a built library exports both functions."""
+    import re
+
     from gaussian_splatting_amd import _lib
 
-    new = {"gsr_render_alpha", "gsr_rasterize_backward_alpha"}
+    new = {"gsr_render_alpha", "gsr_rasterize_backward"}
     assert new <= set(_lib.header_symbols(_lib.HEADER_PATH))
     assert new <= set(_lib.SIGNATURES)
     text = open(_lib.HEADER_PATH).read()
     assert "int gsr_render_alpha(int width, int height, const void* image_buffer, float* out_alpha, void* stream);" in text
-    assert "const float* dL_dinvdepths, const float* dL_dalphas, float* dL_dmean2D" in " ".join(text.split())
+    struct = re.search(r"typedef struct gsr_backward_args \{(.*?)\} gsr_backward_args;", text, flags=re.S).group(1)
+    assert re.search(r"^\s*const float\* dL_dalphas;", struct, flags=re.M)
+    assert "int gsr_rasterize_backward(const gsr_backward_args* args);" in text
+    assert "dL_dalphas" in dict(_lib.BackwardArgs._fields_)
     if os.path.exists(_lib.LIB_PATH):
         out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
         exported = {line.split()[-1] for line in out.splitlines() if line.strip()}

@@ -5,7 +5,7 @@ two exchanges run for real:
 
   * GradArena.all_reduce -- the backward writes the 59-float parameter gradients into the flat arena,
     one all-reduce sums them;
-  * ViewExchange -- each rank writes its view block (gsr_rasterize_backward_screen), one all-gather of the
+  * ViewExchange -- each rank writes its view block (gsr_backward_args.view_block), one all-gather of the
     packed (sparse) blocks -- and of the dense ones, and of the packed blocks in three Gaussian-range chunks
     gathered asynchronously (chunks=3) -- and every rank runs gsr_gauss_backward_views over both views; the
     sparse exchanges again at their capacity hints (no wait for the count), and with a hint forced below

@@ -1,5 +1,5 @@
 """The absolute screen-space gradient on the GPU: ``rasterize_gaussians_backward(..., absgrad=True)`` (include/gsr.h
-gsr_rasterize_backward_abs; the ABSGRAD instantiations of csrc/render.hip render_bwd, gauss_reduce / gauss_bwd in
+gsr_backward_args.dL_dmean2D_abs; the ABSGRAD instantiations of csrc/render.hip render_bwd, gauss_reduce / gauss_bwd in
 csrc/backward.hip) and ``means2D.absgrad`` through the autograd nodes.
 
 Reference: tests/absgrad_ref.py -- one backward of the unchanged oracle per pixel, |dL_dmeans2D[:, :2]| summed in

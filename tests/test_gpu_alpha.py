@@ -1,6 +1,6 @@
 """The accumulated-alpha output on the GPU: ``alpha = 1 - final_T`` [1,H,W] from
 ``rasterize_gaussians(..., return_alpha=True)`` (include/gsr.h gsr_render_alpha; csrc/alpha.hip) and its gradient
-through ``rasterize_gaussians_backward(..., dL_dout_alpha=...)`` (gsr_rasterize_backward_alpha; the seed of the
+through ``rasterize_gaussians_backward(..., dL_dout_alpha=...)`` (gsr_backward_args.dL_dalphas; the seed of the
 per-pixel scalar gB in csrc/render.hip render_bwd).
 
 References: the product's own per-pixel state for the forward's bits, and the unchanged oracle -- the forward's

@@ -352,7 +352,7 @@ def _run_pair(inp, gc, gd):
 @pytest.mark.parametrize("hint", ["previous", "too_small", "too_large"])
 @pytest.mark.record_path
 def test_capacity_forward_matches_sync_forward(hint, monkeypatch):
-    """gsr_rasterize_forward_ex (no mid-forward host sync, binning sized from a capacity hint) gives bitwise
+    """A forward with a capacity hint (gsr_forward_args.capacity_hint: no mid-forward host sync, binning sized from a capacity hint) gives bitwise
     the same results as the reference-style synchronising forward, whether the hint fits, is too small (the
     binning stage is redone) or is far too large (heavy sentinel padding in the sort)."""
     from gaussian_splatting_amd import _C as CM

@@ -1,5 +1,5 @@
-"""Separate-DC SH input: the 3DGS-accel interface (dc + rest, gsr_rasterize_forward_dc /
-gsr_rasterize_backward_dc) that the reference's callers select with separate_sh=True
+"""Separate-DC SH input: the 3DGS-accel interface (dc + rest, include/gsr.h
+gsr_scene.dc) that the reference's callers select with separate_sh=True
 (train.py:41-45,105,144; gaussian_renderer/__init__.py:106-125).
 
 The accel build is not vendored by the reference, so there

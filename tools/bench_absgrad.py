@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measure the absolute screen-space gradient (gsr_rasterize_backward_abs) on one MI355X.
+"""Measure the absolute screen-space gradient (gsr_backward_args.dL_dmean2D_abs) on one MI355X.
 
     python tools/bench_absgrad.py [--config 1m_1080p_sh3] [--reps 30] [--rounds 5] [--bwd-atomic 0|1]
 

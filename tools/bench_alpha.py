@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measure the accumulated-alpha output (gsr_render_alpha, gsr_rasterize_backward_alpha) on one MI355X.
+"""Measure the accumulated-alpha output (gsr_render_alpha, gsr_backward_args.dL_dalphas) on one MI355X.
 
     python tools/bench_alpha.py [--config 1m_1080p_sh3] [--reps 30] [--rounds 5]
 

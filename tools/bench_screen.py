@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the screen-space backward (gsr_rasterize_backward_screen: render_bwd + the step that fills the view
+"""Cost of the screen-space backward (gsr_rasterize_backward with a view block: render_bwd + the step that fills the view
 block) on one MI355X, record path (bwd_atomic=0: records + gauss_reduce) against the atomic path (the default:
 accumulator rows + gauss_live_views), interleaved (development tool).
 
