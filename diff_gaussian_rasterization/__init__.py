@@ -19,10 +19,11 @@ from gaussian_splatting_amd.rasterizer import (  # noqa: F401
     GaussianRasterizationSettings,
     GaussianRasterizer,
     _RasterizeGaussians,
+    _RenderDistortion,
     _RenderFeatures,
     cpu_deep_copy_tuple,
     rasterize_gaussians,
 )
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RenderFeatures", "SparseGaussianAdam", "cpu_deep_copy_tuple", "_C", "ContributionStats", "split", "render_contribution"]
+           "_RenderFeatures", "_RenderDistortion", "SparseGaussianAdam", "cpu_deep_copy_tuple", "_C", "ContributionStats", "split", "render_contribution"]

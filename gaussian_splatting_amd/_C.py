@@ -26,7 +26,8 @@ __all__ = ["rasterize_gaussians", "rasterize_gaussians_backward", "rasterize_gau
            "views_live_floats", "views_live_list",
            "mark_visible", "adamUpdate", "fusedssim",
            "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha", "contribution_stats",
-           "render_features", "render_features_backward", "feature_chunk", "check_features"]
+           "render_features", "render_features_backward", "feature_chunk", "check_features",
+           "render_distortion", "render_distortion_backward", "check_distortion"]
 
 
 # Sync-free forward (gsr_forward_args.capacity_hint): the binning buffer is sized from a capacity
@@ -310,6 +311,88 @@ def render_features_backward(geomBuffer: torch.Tensor, binningBuffer: torch.Tens
             _stream_handle(device))
     _lib.check(rc, "render_features_backward")
     return dL_dF, block
+
+
+def check_distortion(t, P: int, device=None) -> None:
+    """The argument check of every ``distortion=`` entry: a contiguous float32 HIP-device [P] tensor (on ``device``
+    when given)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"distortion: expected a tensor, got {type(t).__name__}")
+    if t.dim() != 1 or t.size(0) != int(P):
+        raise RuntimeError(f"distortion must have dimensions (num_points,), i.e. ({int(P)},); got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"distortion: expected a float32 tensor, got {t.dtype}")
+    _require_device(t, "distortion")
+    if device is not None and t.device != device:
+        raise RuntimeError(f"distortion: tensor on {t.device}, expected {device}")
+    if not t.is_contiguous():
+        raise RuntimeError("distortion: expected a contiguous [P] tensor (call .contiguous())")
+
+
+def render_distortion(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imgBuffer: torch.Tensor,
+                      num_rendered: int, P: int, image_height: int, image_width: int, t: torch.Tensor) -> tuple:
+    """``(distortion_map [1,H,W], moments [2,H,W])`` of the per-Gaussian scalar ``t`` [P] under the weights of the
+    forward that filled the three buffers (include/gsr.h gsr_render_distortion), on the current stream: per pixel
+    ``D = 2 sum_i w_i (t_i A_{i-1} - B_{i-1})`` over its contributors front to back, which is ``sum_{i,j} w_i w_j
+    |t_i - t_j|`` for ``t`` non-decreasing along the list and the signed form otherwise; ``moments`` holds every
+    pixel's ``sum_i w_i`` and ``sum_i w_i (t_i - t_1)`` (about its first contributor) for the backward.  Read-only on the buffers (copies are accepted, a
+    backward may precede or follow), bitwise reproducible; zeros when there are no Gaussians or none was rendered."""
+    P, H, W = int(P), int(image_height), int(image_width)
+    check_distortion(t, P)
+    device = t.device
+    f32 = dict(dtype=torch.float32, device=device)
+    if P == 0:
+        return torch.zeros((1, H, W), **f32), torch.zeros((2, H, W), **f32)
+    dmap, moments = _empty((1, H, W), **f32), _empty((2, H, W), **f32)  # every element is written
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_distortion(P, int(num_rendered), W, H,
+                                               *_feature_buffers(geomBuffer, binningBuffer, imgBuffer),
+                                               t.data_ptr(), dmap.data_ptr(), moments.data_ptr(),
+                                               _stream_handle(device))
+    _lib.check(rc, "render_distortion")
+    return dmap, moments
+
+
+def render_distortion_backward(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imgBuffer: torch.Tensor,
+                               num_rendered: int, P: int, image_height: int, image_width: int, t: torch.Tensor,
+                               distortion_map: torch.Tensor, moments: torch.Tensor, dL_ddistortion_map: torch.Tensor,
+                               geometry=None) -> tuple:
+    """The backward of ``render_distortion`` (include/gsr.h gsr_render_distortion_backward): returns ``(dL_dt [P],
+    view_block)``.  ``geometry`` None (only ``t`` needs a gradient): ``dL_dt`` alone, ``view_block`` is None.
+    Otherwise the dict ``render_features_backward`` takes, and the distortion loss's per-Gaussian screen-space sums
+    are also written, as a view block for ``gauss_backward_views`` exactly as there."""
+    P, H, W = int(P), int(image_height), int(image_width)
+    check_distortion(t, P)
+    device = t.device
+    f32 = dict(dtype=torch.float32, device=device)
+    for name, m, c in (("distortion_map", distortion_map, 1), ("moments", moments, 2),
+                       ("dL_ddistortion_map", dL_ddistortion_map, 1)):
+        if tuple(m.shape) != (c, H, W) or m.dtype != torch.float32 or m.device != device:
+            raise RuntimeError(f"{name}: expected a float32 {(c, H, W)} tensor on {device}, got {m.dtype} "
+                               f"{tuple(m.shape)} on {m.device}")
+    if P == 0:
+        return torch.zeros((0,), **f32), (None if geometry is None else torch.zeros(view_block_floats(0), **f32))
+    ins = _Inputs(device)
+    dL_dt = _empty((P,), **f32)  # every element is written
+    block = None
+    cam = (None, None, None, 0.0, 0.0, 0, None)
+    scratch = torch.empty(0, dtype=torch.uint8, device=device)
+    rs = _Resizer(scratch)
+    if geometry is not None:
+        g = geometry
+        block = _empty((view_block_floats(P),), **f32)
+        campos = g["campos"] if g["campos"].device.type == "cuda" else g["campos"].to(device)
+        cam = (ins.req(g["viewmatrix"], "viewmatrix", small=True), ins.req(g["projmatrix"], "projmatrix", small=True),
+               ins.req(campos, "campos"), float(g["tanfovx"]), float(g["tanfovy"]), int(bool(g["antialiasing"])),
+               ins.radii(g["radii"]))
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_distortion_backward(
+            P, int(num_rendered), W, H, *_feature_buffers(geomBuffer, binningBuffer, imgBuffer), t.data_ptr(),
+            ins.req(distortion_map, "distortion_map"), ins.req(moments, "moments"),
+            ins.req(dL_ddistortion_map, "dL_ddistortion_map"), dL_dt.data_ptr(),
+            block.data_ptr() if block is not None else None, *cam, rs.cb, None, _stream_handle(device))
+    _lib.check(rc, "render_distortion_backward")
+    return dL_dt, block
 
 
 def _scene_view(ins: _Inputs, *, means3D, dc, sh, degree, colors, opacities, scales, scale_modifier, rotations,

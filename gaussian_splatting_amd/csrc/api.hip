@@ -1313,6 +1313,57 @@ int features_args(const char* who, int P, int C, int R, int width, int height, c
     *walk = true;
     return GSR_OK;
 }
+
+// The view-block tail the feature and distortion backwards share.  view_block_check: the arguments a view block needs.
+int view_block_check(const char* who, const float* view_block, const float* viewmatrix, const float* projmatrix,
+                     const float* campos, const int* radii, const void* geom_buffer) {
+    using namespace gsr;
+    if (!view_block) return GSR_OK;
+    if ((reinterpret_cast<uintptr_t>(view_block) & 15) != 0)
+        return fail(GSR_ERR_ARGUMENT, "%s: view block must be 16-byte aligned", who);
+    if (!viewmatrix || !projmatrix || !campos || !radii || !geom_buffer)
+        return fail(GSR_ERR_ARGUMENT, "%s: the view block needs the camera, radii and the geometry buffer", who);
+    return GSR_OK;
+}
+
+// Scratch accumulator rows and touched bits, zeroed (gauss_live_views leaves them zero again).
+int view_scratch(const char* who, int P, gsr_alloc_fn scratch_alloc, void* scratch_ctx, hipStream_t stream,
+                 float4** acc, uint32_t** touched) {
+    using namespace gsr;
+    Carver c{nullptr, 0};
+    c.take<float4>((size_t)kAccRow4 * P);
+    c.take<uint32_t>(touched_words((size_t)P));
+    const size_t bytes = align_up(c.off);
+    char* base = (char*)call_alloc(scratch_alloc, scratch_ctx, bytes);
+    if (!base) return fail(GSR_ERR_ALLOC, "%s: scratch allocation failed", who);
+    Carver d{base, 0};
+    *acc = d.take<float4>((size_t)kAccRow4 * P);
+    *touched = d.take<uint32_t>(touched_words((size_t)P));
+    HIP_TRY(hipMemsetAsync(base, 0, bytes, stream), who);
+    return GSR_OK;
+}
+
+// The view block of one such loss alone, from the accumulator rows its kernel added into: colour and inverse-depth
+// sums zero, the flags from radii and the forward's SH clamp bits, the camera header (no inverse-depth term).
+int view_block_finish(const char* who, int P, int width, int height, float* view_block, uint32_t* touched, float4* acc,
+                      const int* radii, const void* geom_buffer, const float* viewmatrix, const float* projmatrix,
+                      const float* campos, float tan_fovx, float tan_fovy, int antialiasing, hipStream_t stream) {
+    using namespace gsr;
+    float* body = view_block + kViewBlockHeader;
+    GradRecs sums{};
+    sums.a = reinterpret_cast<float4*>(body);
+    sums.b = reinterpret_cast<float4*>(body + 4 * (size_t)P);
+    sums.c = reinterpret_cast<float2*>(body + 8 * (size_t)P);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(body + 10 * (size_t)P);
+    HIP_TRY(launch_gauss_live_views(P, touched, acc, radii, geom_clamped(geom_buffer, P, width, height), sums, flags,
+                                    stream),
+            who);
+    const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
+    HIP_TRY(launch_view_header(view_block, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, focal_x, focal_y,
+                               antialiasing, 0, stream),
+            who);
+    return GSR_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1361,28 +1412,15 @@ int gsr_render_features_backward(int P, int C, int R, int width, int height, con
     if (P == 0) return GSR_OK;
     if (!features || !dL_dout_features || !dL_dfeatures || (view_block && !out_features))
         return fail(GSR_ERR_ARGUMENT, "render_features_backward: null pointer");
-    if (view_block) {
-        if ((reinterpret_cast<uintptr_t>(view_block) & 15) != 0)
-            return fail(GSR_ERR_ARGUMENT, "render_features_backward: view block must be 16-byte aligned");
-        if (!viewmatrix || !projmatrix || !campos || !radii || !geom_buffer)
-            return fail(GSR_ERR_ARGUMENT, "render_features_backward: the view block needs the camera, radii and the "
-                                          "geometry buffer");
-    }
+    if (int rc = view_block_check("render_features_backward", view_block, viewmatrix, projmatrix, campos, radii,
+                                  geom_buffer))
+        return rc;
     HIP_TRY(hipMemsetAsync(dL_dfeatures, 0, sizeof(float) * (size_t)P * C, stream), "render_features_backward zero");
     float4* acc = nullptr;
     uint32_t* touched = nullptr;
-    if (view_block) {  // scratch accumulator rows and touched bits, zeroed (gauss_live_views leaves them zero again)
-        Carver c{nullptr, 0};
-        c.take<float4>((size_t)kAccRow4 * P);
-        c.take<uint32_t>(touched_words((size_t)P));
-        const size_t bytes = align_up(c.off);
-        char* base = (char*)call_alloc(scratch_alloc, scratch_ctx, bytes);
-        if (!base) return fail(GSR_ERR_ALLOC, "render_features_backward: scratch allocation failed");
-        Carver d{base, 0};
-        acc = d.take<float4>((size_t)kAccRow4 * P);
-        touched = d.take<uint32_t>(touched_words((size_t)P));
-        HIP_TRY(hipMemsetAsync(base, 0, bytes, stream), "render_features_backward scratch zero");
-    }
+    if (view_block)
+        if (int rc = view_scratch("render_features_backward", P, scratch_alloc, scratch_ctx, stream, &acc, &touched))
+            return rc;
     if (walk) {
         fa.features = features;
         fa.fmap = out_features;
@@ -1392,27 +1430,84 @@ int gsr_render_features_backward(int P, int C, int R, int width, int height, con
         fa.touched = touched;
         HIP_TRY(launch_features_bwd(fa, stream), "render_features_backward");
     }
-    if (view_block) {
-        // the view block of this loss alone: colour and inverse-depth sums zero, the flags from radii and the
-        // forward's SH clamp bits, the camera header (no inverse-depth term)
-        float* body = view_block + kViewBlockHeader;
-        GradRecs sums{};
-        sums.a = reinterpret_cast<float4*>(body);
-        sums.b = reinterpret_cast<float4*>(body + 4 * (size_t)P);
-        sums.c = reinterpret_cast<float2*>(body + 8 * (size_t)P);
-        uint32_t* flags = reinterpret_cast<uint32_t*>(body + 10 * (size_t)P);
-        HIP_TRY(launch_gauss_live_views(P, touched, acc, radii, geom_clamped(geom_buffer, P, width, height), sums, flags,
-                                        stream),
-                "render_features_backward view block");
-        const float focal_y = height / (2.0f * tan_fovy), focal_x = width / (2.0f * tan_fovx);
-        HIP_TRY(launch_view_header(view_block, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, focal_x, focal_y,
-                                   antialiasing, 0, stream),
-                "render_features_backward view header");
-    }
+    if (view_block)
+        return view_block_finish("render_features_backward", P, width, height, view_block, touched, acc, radii,
+                                 geom_buffer, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, antialiasing, stream);
     return GSR_OK;
 }
 
 int gsr_render_features_chunk(void) { return gsr::kFeatChunk; }
+
+// The distortion pair is the feature pair over one scalar per Gaussian: the same argument rules (features_args with
+// C = 1), the same walk, the same view-block tail.
+int gsr_render_distortion(int P, int R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                          const void* image_buffer, int binning_capacity, size_t binning_bytes, const float* t,
+                          float* out_distortion, float* out_moments, void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    DistortionArgs da{};
+    bool walk = false;
+    if (int rc = features_args("render_distortion", P, 1, R, width, height, geom_buffer, binning_buffer, image_buffer,
+                               binning_capacity, binning_bytes, &da.walk, &walk))
+        return rc;
+    if (!out_distortion || !out_moments || (P > 0 && !t))
+        return fail(GSR_ERR_ARGUMENT, "render_distortion: null pointer");
+    if (!walk) {
+        const size_t N = (size_t)width * height;
+        HIP_TRY(hipMemsetAsync(out_distortion, 0, sizeof(float) * N, stream), "render_distortion zero");
+        HIP_TRY(hipMemsetAsync(out_moments, 0, sizeof(float) * 2 * N, stream), "render_distortion zero");
+        return GSR_OK;
+    }
+    da.walk.features = t;
+    da.walk.out = out_distortion;
+    da.moments = out_moments;
+    HIP_TRY(launch_distortion_fwd(da, stream), "render_distortion");
+    return GSR_OK;
+}
+
+int gsr_render_distortion_backward(int P, int R, int width, int height, const void* geom_buffer,
+                                   const void* binning_buffer, const void* image_buffer, int binning_capacity,
+                                   size_t binning_bytes, const float* t, const float* out_distortion,
+                                   const float* out_moments, const float* dL_dout_distortion, float* dL_dt,
+                                   float* view_block, const float* viewmatrix, const float* projmatrix,
+                                   const float* campos, float tan_fovx, float tan_fovy, int antialiasing,
+                                   const int* radii, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    DistortionArgs da{};
+    bool walk = false;
+    if (int rc = features_args("render_distortion_backward", P, 1, R, width, height, geom_buffer, binning_buffer,
+                               image_buffer, binning_capacity, binning_bytes, &da.walk, &walk))
+        return rc;
+    if (P == 0) return GSR_OK;
+    if (!t || !out_moments || !dL_dout_distortion || !dL_dt || (view_block && !out_distortion))
+        return fail(GSR_ERR_ARGUMENT, "render_distortion_backward: null pointer");
+    if (int rc = view_block_check("render_distortion_backward", view_block, viewmatrix, projmatrix, campos, radii,
+                                  geom_buffer))
+        return rc;
+    HIP_TRY(hipMemsetAsync(dL_dt, 0, sizeof(float) * (size_t)P, stream), "render_distortion_backward zero");
+    float4* acc = nullptr;
+    uint32_t* touched = nullptr;
+    if (view_block)
+        if (int rc = view_scratch("render_distortion_backward", P, scratch_alloc, scratch_ctx, stream, &acc, &touched))
+            return rc;
+    if (walk) {
+        da.walk.features = t;
+        da.walk.fmap = out_distortion;
+        da.walk.dL_dfmap = dL_dout_distortion;
+        da.walk.dL_dfeatures = dL_dt;
+        da.walk.acc = reinterpret_cast<float*>(acc);
+        da.walk.touched = touched;
+        da.moments = const_cast<float*>(out_moments);  // (read only)
+        HIP_TRY(launch_distortion_bwd(da, stream), "render_distortion_backward");
+    }
+    if (view_block)
+        return view_block_finish("render_distortion_backward", P, width, height, view_block, touched, acc, radii,
+                                 geom_buffer, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, antialiasing, stream);
+    return GSR_OK;
+}
 
 int gsr_debug_forward_state(int P, int width, int height, int R, int binning_capacity, size_t binning_bytes,
                             const void* geom_buffer, const void* binning_buffer, const void* image_buffer,

@@ -163,6 +163,16 @@ struct FeatureArgs {
     uint32_t* touched;            // caller, and their touched bits; both null: no geometry part
 };
 
+// Depth-distortion map (distortion.hip, include/gsr.h gsr_render_distortion / gsr_render_distortion_backward): the
+// feature walk over one scalar t per Gaussian, one wave per tile.
+struct DistortionArgs {
+    // as the feature calls fill it, with C = 1: features = t [P], out / fmap = the map D [H,W], dL_dfmap = dL/dD
+    // [H,W], dL_dfeatures = dL_dt [P] (zeroed by the caller, added into), acc / touched as there
+    FeatureArgs walk;
+    float* moments;               // [2,H,W]: every pixel's A_n and B_n (about its first contributor's t); the forward
+                                  // writes them, the backward reads them
+};
+
 struct GaussBwdArgs {
     int P, D, M, W, H;
     const float* means3D;
@@ -499,6 +509,9 @@ hipError_t launch_contrib_stats(const ContribArgs& a, size_t max_units, hipStrea
 // features.hip: one wave per (tile, channel chunk); the backward's geometry variant is picked by FeatureArgs::acc
 hipError_t launch_features_fwd(const FeatureArgs& a, hipStream_t stream);
 hipError_t launch_features_bwd(const FeatureArgs& a, hipStream_t stream);
+// distortion.hip: one wave per tile; the backward's geometry variant is picked by DistortionArgs::walk.acc
+hipError_t launch_distortion_fwd(const DistortionArgs& a, hipStream_t stream);
+hipError_t launch_distortion_bwd(const DistortionArgs& a, hipStream_t stream);
 // Longest reachable prefix K4 sorts ("sort_prefix" option range; binning.hip kPrefixBuf holds twice it).
 constexpr uint32_t kSortPrefixMax = 1024;
 // backward.hip

@@ -14,7 +14,7 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansCamera", "_RenderFeatures", "cpu_deep_copy_tuple"]
+           "_RasterizeGaussiansCamera", "_RenderFeatures", "_RenderDistortion", "cpu_deep_copy_tuple"]
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -40,9 +40,10 @@ class GaussianRasterizationSettings(NamedTuple):
     antialiasing: bool
 
 
-def _rasterize_with_features(args, features, kw):
-    """``rasterize_gaussians(..., features=F)``: the render without the keyword, whose node hands its buffers over, then
-    the feature node behind it; ``feature_map`` goes after ``alpha`` and before the contribution statistics."""
+def _rasterize_with_maps(args, features, distortion, kw):
+    """``rasterize_gaussians(..., features=F, distortion=t)`` (either or both): the render without the keywords, whose
+    node hands its buffers over, then the feature and / or distortion node behind it; ``feature_map`` then
+    ``distortion_map`` go after ``alpha`` and before the contribution statistics."""
     means3D, means2D = args[0], args[1]
     s = args[-1]
     scales, rotations, cov3D = args[-4], args[-3], args[-2]
@@ -53,25 +54,66 @@ def _rasterize_with_features(args, features, kw):
     geom_in = (means3D, means2D, opacities, scales, rotations)
     if has_cov and torch.is_grad_enabled() and any(
             isinstance(t, torch.Tensor) and t.requires_grad for t in geom_in + (cov3D,)):
-        raise RuntimeError("features= with cov3D_precomp cannot give a geometry gradient of the feature loss (its "
+        kws = " / ".join(k for k, v in (("features=", features), ("distortion=", distortion)) if v is not None)
+        loss = "feature" if distortion is None else "distortion" if features is None else "feature / distortion"
+        raise RuntimeError(f"{kws} with cov3D_precomp cannot give a geometry gradient of the {loss} loss (its "
                            "per-Gaussian backward needs scales and rotations): detach the geometry inputs for this "
                            "render, or pass scales and rotations")
-    _C.check_features(features, means3D.size(0), means3D.device if means3D.device.type == "cuda" else None)
-    _RasterizeGaussians._features.value = True  # (read by the node's forward, which leaves its buffers there)
+    device = means3D.device if means3D.device.type == "cuda" else None
+    if features is not None:
+        _C.check_features(features, means3D.size(0), device)
+    if distortion is not None:
+        _C.check_distortion(distortion, means3D.size(0), device)
+    _RasterizeGaussians._handover.value = True  # (read by the node's forward, which leaves its buffers there)
     try:
         outs = rasterize_gaussians(*args, **kw)
-        handed = getattr(_RasterizeGaussians._features, "value", None)
+        handed = getattr(_RasterizeGaussians._handover, "value", None)
     finally:
-        _RasterizeGaussians._features.value = None
+        _RasterizeGaussians._handover.value = None
     if not isinstance(handed, tuple):
-        raise RuntimeError("rasterize_gaussians(features=): the render did not hand over its buffers")
-    geom, binning, img, num_rendered = handed
+        raise RuntimeError("rasterize_gaussians(features= / distortion=): the render did not hand over its buffers")
     empty = means3D.new_empty(0)
-    fmap = _RenderFeatures.apply(features, means3D, means2D, opacities,
-                                 empty if has_cov else scales, empty if has_cov else rotations,
-                                 outs[1], geom, binning, img, s, num_rendered)
+    tail = (means3D, means2D, opacities, empty if has_cov else scales, empty if has_cov else rotations, outs[1],
+            *handed[:3], s, handed[3])  # both nodes receive the buffers of the one render
+    maps = ()
+    if features is not None:
+        maps += (_RenderFeatures.apply(features, *tail),)
+    if distortion is not None:
+        maps += (_RenderDistortion.apply(distortion, *tail),)
     n = 4 if kw.get("return_alpha") else 3
-    return outs[:n] + (fmap,) + outs[n:]
+    return outs[:n] + maps + outs[n:]
+
+
+def _geometry_of(ctx, s, radii):
+    """The ``geometry`` argument of a map node's native backward: the camera and radii when a geometry input of the
+    node needs a gradient, else None."""
+    if not any(ctx.needs_input_grad[1:6]):
+        return None
+    return dict(viewmatrix=s.viewmatrix.detach(), projmatrix=s.projmatrix.detach(), campos=s.campos.detach(),
+                tanfovx=s.tanfovx, tanfovy=s.tanfovy, antialiasing=s.antialiasing, radii=radii)
+
+
+def _map_node_grads(ctx, s, grad_first, block, means3D, opacities, scales, rotations):
+    """A map node's backward tuple: the gradient of its first input, then, from the view block of its loss alone
+    (``_C.gauss_backward_views``), those of ``means3D, means2D, opacities, scales, rotations``; None for the rest."""
+    grad_first = grad_first if ctx.needs_input_grad[0] else None
+    if block is None:
+        return (grad_first,) + (None,) * 11
+    P = means3D.size(0)
+    f32 = dict(dtype=torch.float32, device=means3D.device)
+    out = {"dL_dmeans3D": torch.empty((P, 3), **f32), "dL_ddc": torch.empty((P, 1, 3), **f32),
+           "dL_dsh": torch.empty((P, 0, 3), **f32), "dL_dopacity": torch.empty((P, 1), **f32),
+           "dL_dscales": torch.empty((P, 3), **f32), "dL_drotations": torch.empty((P, 4), **f32)}
+    grad_means2D = torch.zeros((P, 3), **f32)
+    if P > 0:
+        # the view block carries no colour gradient: a zero dc of one coefficient satisfies the SH reads
+        _C.gauss_backward_views(means3D, torch.zeros((P, 1, 3), **f32), None, 0, opacities, scales, rotations,
+                                s.scale_modifier, block.view(1, -1), out)
+        grad_means2D[:, :2] = block[64 + 4 * P:64 + 8 * P].view(P, 4)[:, :2]
+    need = ctx.needs_input_grad
+    return (grad_first, out["dL_dmeans3D"] if need[1] else None, grad_means2D if need[2] else None,
+            out["dL_dopacity"].view(opacities.shape) if need[3] else None,
+            out["dL_dscales"] if need[4] else None, out["dL_drotations"] if need[5] else None) + (None,) * 6
 
 
 class _RenderFeatures(torch.autograd.Function):
@@ -96,38 +138,47 @@ class _RenderFeatures(torch.autograd.Function):
         s = ctx.raster_settings
         features, fmap, means3D, opacities, scales, rotations, radii, geom, binning, img = ctx.saved_tensors
         P = means3D.size(0)
-        need_geom = any(ctx.needs_input_grad[1:6])
-        if need_geom and P > 0 and (scales.numel() == 0 or rotations.numel() == 0):
+        geometry = _geometry_of(ctx, s, radii)
+        if geometry is not None and P > 0 and (scales.numel() == 0 or rotations.numel() == 0):
             raise RuntimeError("features=: a geometry gradient of the feature loss needs scales and rotations")
-        geometry = None
-        if need_geom:
-            geometry = dict(viewmatrix=s.viewmatrix.detach(), projmatrix=s.projmatrix.detach(),
-                            campos=s.campos.detach(), tanfovx=s.tanfovx, tanfovy=s.tanfovy,
-                            antialiasing=s.antialiasing, radii=radii)
         dL_dF, block = _C.render_features_backward(geom, binning, img, ctx.num_rendered, P, s.image_height,
                                                    s.image_width, features, fmap, grad_fmap.contiguous(),
                                                    geometry=geometry)
-        grad_F = dL_dF if ctx.needs_input_grad[0] else None
-        if not need_geom:
-            return (grad_F,) + (None,) * 11
-        f32 = dict(dtype=torch.float32, device=means3D.device)
-        out = {"dL_dmeans3D": torch.empty((P, 3), **f32), "dL_ddc": torch.empty((P, 1, 3), **f32),
-               "dL_dsh": torch.empty((P, 0, 3), **f32), "dL_dopacity": torch.empty((P, 1), **f32),
-               "dL_dscales": torch.empty((P, 3), **f32), "dL_drotations": torch.empty((P, 4), **f32)}
-        grad_means2D = torch.zeros((P, 3), **f32)
-        if P > 0:
-            # the view block carries no colour gradient: a zero dc of one coefficient satisfies the SH reads
-            _C.gauss_backward_views(means3D, torch.zeros((P, 1, 3), **f32), None, 0, opacities, scales, rotations,
-                                    s.scale_modifier, block.view(1, -1), out)
-            grad_means2D[:, :2] = block[64 + 4 * P:64 + 8 * P].view(P, 4)[:, :2]
-        need = ctx.needs_input_grad
-        return (grad_F, out["dL_dmeans3D"] if need[1] else None, grad_means2D if need[2] else None,
-                out["dL_dopacity"].view(opacities.shape) if need[3] else None,
-                out["dL_dscales"] if need[4] else None, out["dL_drotations"] if need[5] else None) + (None,) * 6
+        return _map_node_grads(ctx, s, dL_dF, block, means3D, opacities, scales, rotations)
+
+
+class _RenderDistortion(torch.autograd.Function):
+    """The distortion node behind the rasterizer node, built like ``_RenderFeatures``: forward =
+    ``_C.render_distortion`` over the rasterizer node's buffers, backward = ``_C.render_distortion_backward`` and,
+    when a geometry input needs a gradient, ``_C.gauss_backward_views`` over the one view block it fills.  Inputs
+    ``(t, means3D, means2D, opacities, scales, rotations, radii, geom, binning, img, raster_settings,
+    num_rendered)``; the per-pixel moments the backward needs stay inside the node."""
+
+    @staticmethod
+    def forward(ctx, t, means3D, means2D, opacities, scales, rotations, radii, geom, binning, img, s, num_rendered):
+        dmap, moments = _C.render_distortion(geom, binning, img, num_rendered, means3D.size(0), s.image_height,
+                                             s.image_width, t)
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(t, dmap, moments, means3D, opacities, scales, rotations, radii, geom, binning, img)
+        return dmap
+
+    @staticmethod
+    def backward(ctx, grad_dmap):
+        s = ctx.raster_settings
+        t, dmap, moments, means3D, opacities, scales, rotations, radii, geom, binning, img = ctx.saved_tensors
+        P = means3D.size(0)
+        geometry = _geometry_of(ctx, s, radii)
+        if geometry is not None and P > 0 and (scales.numel() == 0 or rotations.numel() == 0):
+            raise RuntimeError("distortion=: a geometry gradient of the distortion loss needs scales and rotations")
+        dL_dt, block = _C.render_distortion_backward(geom, binning, img, ctx.num_rendered, P, s.image_height,
+                                                     s.image_width, t, dmap, moments, grad_dmap.contiguous(),
+                                                     geometry=geometry)
+        return _map_node_grads(ctx, s, dL_dt, block, means3D, opacities, scales, rotations)
 
 
 def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib=False, contrib_weight=None,
-                        features=None):
+                        features=None, distortion=None):
     """``rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
     raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``.
 
@@ -153,13 +204,26 @@ def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib
     node (``_RenderFeatures``), to ``means3D``, ``opacities``, ``scales``, ``rotations`` and ``means2D`` (so
     ``means2D.grad`` carries the feature loss too); when only ``F`` requires grad the backward does the ``F`` work
     alone.  The feature loss does not reach the camera tensors or ``means2D.absgrad``; with ``cov3D_precomp`` a
-    geometry input that requires grad is refused.  Without the keyword nothing more is launched or allocated."""
+    geometry input that requires grad is refused.  Without the keyword nothing more is launched or allocated.
+
+    ``distortion=t`` (an extension, the Mip-NeRF 360 / 2DGS / gsplat ``distloss`` term): ``t`` a contiguous float32
+    [P] device tensor of the caller's choice (view depth, ``1/z``, a contracted distance).  One more output
+    ``distortion_map`` [1,H,W], after ``feature_map`` when that is present and before the contribution statistics:
+    per pixel ``D = 2 sum_i w_i (t_i A_{i-1} - B_{i-1})`` over its contributors front to back with this render's own
+    blend weights (``A``, ``B`` the running sums of ``w`` and ``w t``; include/gsr.h gsr_render_distortion).  That is
+    ``sum_{i,j} w_i w_j |t_i - t_j|`` whenever ``t`` is non-decreasing along the blend order (any increasing function
+    of view depth) and the SIGNED form ``2 sum_{i behind j} w_i w_j (t_i - t_j)`` otherwise; no background term.
+    Differentiable with respect to ``t`` (so to whatever torch built it from, ``means3D`` and camera tensors
+    included) and, through an autograd node of its own (``_RenderDistortion``), to the geometry exactly as
+    ``features=``, with the same limits: the kernel's geometry part does not reach the camera tensors or
+    ``means2D.absgrad``, and ``cov3D_precomp`` with a geometry input that requires grad is refused.  Without the
+    keyword nothing more is launched or allocated."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
-    if features is not None:
-        return _rasterize_with_features(args, features, dict(return_alpha=return_alpha, absgrad=absgrad,
-                                                             return_contrib=return_contrib,
-                                                             contrib_weight=contrib_weight))
+    if features is not None or distortion is not None:
+        return _rasterize_with_maps(args, features, distortion,
+                                    dict(return_alpha=return_alpha, absgrad=absgrad, return_contrib=return_contrib,
+                                         contrib_weight=contrib_weight))
     _RasterizeGaussians._return_alpha.value = bool(return_alpha)  # (read and cleared by the node's forward)
     _RasterizeGaussians._absgrad.value = bool(absgrad)            # (likewise)
     if contrib_weight is not None and not return_contrib:
@@ -194,7 +258,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     _return_alpha = threading.local()  # set by rasterize_gaussians(..., return_alpha=True) for its one call
     _absgrad = threading.local()       # set by rasterize_gaussians(..., absgrad=True) for its one call
     _contrib = threading.local()       # set by rasterize_gaussians(..., return_contrib=True): (contrib_weight,)
-    _features = threading.local()      # True for a call with features=; the forward replaces it by its buffers
+    _handover = threading.local()      # True for a call with features= / distortion=; the forward leaves its buffers
 
     @staticmethod
     def _absgrad_kw(ctx):
@@ -260,9 +324,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         saved = (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geom, binning, img)
         ctx.save_for_backward(*saved, *(() if dc is None else (dc,)))
         outs = (color, radii, invdepths, alpha) if with_alpha else (color, radii, invdepths)
-        if getattr(_RasterizeGaussians._features, "value", None) is True:
-            # features=: the buffers saved above are handed to the feature node (rasterize_gaussians), nothing else
-            _RasterizeGaussians._features.value = (geom, binning, img, num_rendered)
+        if getattr(_RasterizeGaussians._handover, "value", None) is True:
+            # features= / distortion=: the buffers saved above are handed to the nodes behind this one
+            # (rasterize_gaussians), nothing else
+            _RasterizeGaussians._handover.value = (geom, binning, img, num_rendered)
         if contrib is None:
             ctx.mark_non_differentiable(radii)
             return outs
@@ -365,7 +430,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, dc=None, return_alpha=False, absgrad=False, return_contrib=False,
-                contrib_weight=None, features=None):
+                contrib_weight=None, features=None, distortion=None):
         """Same checks as the reference (:242-261).  ``dc=`` (keyword) selects the 3DGS-accel separate-SH
         input: ``dc`` = ``_features_dc`` [P,1,3] and ``shs`` = ``_features_rest`` [P,M,3]
         (gaussian_renderer/__init__.py:115-125).  ``return_alpha=True`` returns ``(color, radii, invdepths,
@@ -373,7 +438,8 @@ class GaussianRasterizer(nn.Module):
         ``absgrad=True``: the backward also sets ``means2D.absgrad`` (``rasterize_gaussians``).
         ``return_contrib=True`` [+ ``contrib_weight=``]: the per-Gaussian contribution statistics [P,4] as the last
         output (``rasterize_gaussians``).  ``features=`` [P,C]: one more differentiable output ``feature_map``
-        [C,H,W], after ``alpha`` and before the statistics (``rasterize_gaussians``)."""
+        [C,H,W], after ``alpha`` and before the statistics; ``distortion=`` [P]: one more differentiable output
+        ``distortion_map`` [1,H,W], after ``feature_map`` (``rasterize_gaussians``)."""
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -391,6 +457,8 @@ class GaussianRasterizer(nn.Module):
             {} if contrib_weight is None else dict(contrib_weight=contrib_weight))
         if features is not None:
             contrib_kw = dict(contrib_kw, features=features)
+        if distortion is not None:
+            contrib_kw = dict(contrib_kw, distortion=distortion)
         if dc is None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad, **contrib_kw)

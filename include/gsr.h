@@ -306,6 +306,48 @@ int gsr_render_features_backward(int P, int C, int R, int width, int height, con
                                  const int* radii, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream);
 int gsr_render_features_chunk(void);
 
+/* Depth-distortion map (the Mip-NeRF 360 distortion regulariser as 2DGS, GOF, RaDe-GS, PGSR and gsplat's distloss use
+ * it): a per-pixel quantity QUADRATIC in the blend weights, which no choice of features can give.  t [P] (float32) is
+ * a per-Gaussian scalar of the caller's choice (view depth, 1/z, a contracted distance).  For a pixel let 1..n be its
+ * contributing entries in the forward's list order, front to back -- the (pixel, Gaussian) pairs of gsr_contrib_stats
+ * with the weights w_i = alpha_i T_i the forward used:
+ *     D = 2 sum_i w_i (t_i A_{i-1} - B_{i-1}),    A_k = sum_{j<=k} w_j,    B_k = sum_{j<=k} w_j t_j
+ * the ordered form 2 sum_{i behind j} w_i w_j (t_i - t_j) (gsplat's convention, one front-to-back pass).  It equals
+ * sum_{i,j} w_i w_j |t_i - t_j| whenever t is non-decreasing along the list (any increasing function of view depth);
+ * for other t it is the SIGNED form.  No background term.
+ *
+ * gsr_render_distortion: from the three buffers of a finished forward (as gsr_render_features takes them, under the
+ *   same conditions) and t into out_distortion ([H,W]) and out_moments ([2,H,W], which the backward takes as input:
+ *   A_n of every pixel and its B_n taken about the pixel's first contributor, sum_i w_i (t_i - t_1) -- D depends on
+ *   differences of t only, and the kernels work in that frame so that float32 loses nothing to the size of t itself),
+ *   every element written; a pixel no Gaussian reaches is 0.0 exactly, and P == 0 or R == 0
+ *   gives zeros (the buffers may then be NULL).  Each pixel is written by one wave, nothing is added atomically: the
+ *   map is bitwise reproducible, and the same bits after a half-tile, a whole-tile or a no_backward forward and for
+ *   copies of the buffers.  Read-only on the buffers and repeatable.  Argument rules and error codes are
+ *   gsr_render_features' (with C = 1).
+ * gsr_render_distortion_backward: the backward of that map for the upstream gradient dL_dout_distortion ([H,W]).
+ *   Writes every element of dL_dt ([P]): with the prefix sums taken BEFORE entry i,
+ *     dD/dt_i = 2 w_i (2 A_prev + w_i - A_n).
+ *   With view_block != NULL it also forms the geometry part: with g_i = dD/dw_i = 2 (t_i (2 A_prev - A_n) + B_n -
+ *   2 B_prev) and sum_h w_h g_h = 2 D (D is homogeneous of degree 2 in w),
+ *     dL/dalpha_i = U (T_i g_i - (2 D - sum_{h<=i} w_h g_h) / (1 - alpha_i)),
+ *   then exactly gsr_render_features_backward's chain and outputs: a view block of this loss alone for
+ *   gsr_gauss_backward_views, the same use of the camera, radii and the scratch callback, the same conventions (no
+ *   gradient through skips, termination or the 0.99 clamp), the same things not covered.  view_block == NULL (only
+ *   t needs a gradient): dL_dt alone, and out_distortion, the camera, radii and the scratch callback are not used.
+ *   Per-Gaussian sums are added with float atomics, in the hardware's order: not bitwise reproducible. */
+int gsr_render_distortion(int P, int R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                          const void* image_buffer, int binning_capacity, size_t binning_bytes,
+                          const float* t /* [P] */, float* out_distortion /* [H,W] */,
+                          float* out_moments /* [2,H,W] */, void* stream);
+int gsr_render_distortion_backward(int P, int R, int width, int height, const void* geom_buffer,
+                                   const void* binning_buffer, const void* image_buffer, int binning_capacity,
+                                   size_t binning_bytes, const float* t, const float* out_distortion,
+                                   const float* out_moments, const float* dL_dout_distortion, float* dL_dt /* [P] */,
+                                   float* view_block /* or NULL */, const float* viewmatrix, const float* projmatrix,
+                                   const float* campos, float tan_fovx, float tan_fovy, int antialiasing,
+                                   const int* radii, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream);
+
 /* Multi-GPU view exchange (gaussian_splatting_amd/distributed.py
  * ViewExchange).  The reference trains on one GPU; sharding views over N ranks needs the
  * N views' parameter gradients summed on every rank.  Instead of all-reducing the 59-float
