@@ -21,9 +21,10 @@ from gaussian_splatting_amd.rasterizer import (  # noqa: F401
     _RasterizeGaussians,
     _RenderDistortion,
     _RenderFeatures,
+    _RenderMedian,
     cpu_deep_copy_tuple,
     rasterize_gaussians,
 )
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RenderFeatures", "_RenderDistortion", "SparseGaussianAdam", "cpu_deep_copy_tuple", "_C", "ContributionStats", "split", "render_contribution"]
+           "_RenderFeatures", "_RenderDistortion", "_RenderMedian", "SparseGaussianAdam", "cpu_deep_copy_tuple", "_C", "ContributionStats", "split", "render_contribution"]

@@ -27,7 +27,8 @@ __all__ = ["rasterize_gaussians", "rasterize_gaussians_backward", "rasterize_gau
            "mark_visible", "adamUpdate", "fusedssim",
            "fusedssim_backward", "forward_rebuilds", "debug_forward_state", "render_alpha", "contribution_stats",
            "render_features", "render_features_backward", "feature_chunk", "check_features",
-           "render_distortion", "render_distortion_backward", "check_distortion"]
+           "render_distortion", "render_distortion_backward", "check_distortion",
+           "render_select", "render_median_backward", "check_median", "check_topk", "select_max_k"]
 
 
 # Sync-free forward (gsr_forward_args.capacity_hint): the binning buffer is sized from a capacity
@@ -393,6 +394,105 @@ def render_distortion_backward(geomBuffer: torch.Tensor, binningBuffer: torch.Te
             block.data_ptr() if block is not None else None, *cam, rs.cb, None, _stream_handle(device))
     _lib.check(rc, "render_distortion_backward")
     return dL_dt, block
+
+
+def select_max_k() -> int:
+    """The largest ``topk=`` this build supports (include/gsr.h gsr_render_select_max_k)."""
+    return int(_lib.load().gsr_render_select_max_k())
+
+
+def check_median(t, P: int, device=None) -> None:
+    """The argument check of every ``median=`` entry: a contiguous float32 HIP-device [P] tensor (on ``device`` when
+    given), as ``check_distortion``."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"median: expected a tensor, got {type(t).__name__}")
+    if t.dim() != 1 or t.size(0) != int(P):
+        raise RuntimeError(f"median must have dimensions (num_points,), i.e. ({int(P)},); got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"median: expected a float32 tensor, got {t.dtype}")
+    _require_device(t, "median")
+    if device is not None and t.device != device:
+        raise RuntimeError(f"median: tensor on {t.device}, expected {device}")
+    if not t.is_contiguous():
+        raise RuntimeError("median: expected a contiguous [P] tensor (call .contiguous())")
+
+
+def check_topk(K) -> int:
+    """The argument check of every ``topk=`` entry: an int (not a bool) in ``1 .. select_max_k()``; returns it."""
+    if isinstance(K, bool) or not isinstance(K, int):
+        raise TypeError(f"topk: expected an int, got {type(K).__name__}")
+    top = select_max_k()
+    if not 1 <= K <= top:
+        raise ValueError(f"topk: expected 1 <= K <= {top}, got {K}")
+    return K
+
+
+def render_select(geomBuffer: torch.Tensor, binningBuffer: torch.Tensor, imgBuffer: torch.Tensor, num_rendered: int,
+                  P: int, image_height: int, image_width: int, t: Optional[torch.Tensor] = None, topk: int = 0,
+                  device=None) -> tuple:
+    """``(median_map [1,H,W] f32, median_ids [1,H,W] i32, topk_ids [K,H,W] i32, topk_weights [K,H,W] f32)`` of the
+    forward that filled the three buffers (include/gsr.h gsr_render_select), in one pass on the current stream; the
+    first two are None without ``t`` and the last two without ``topk``.  Per pixel the median contributor is the last
+    one blended while the transmittance is above one half, ``median_map`` the copy of its ``t``; the top-K are the
+    contributors of largest blend weight, descending, earlier first on ties.  No contributor / rank beyond the count:
+    id -1, value 0.  Read-only on the buffers (copies are accepted, a backward may precede or follow), bitwise
+    reproducible, not differentiable (``render_median_backward`` is the scatter to ``t``).  ``device``: where the
+    buffers live, needed only without ``t``."""
+    P, H, W = int(P), int(image_height), int(image_width)
+    K = check_topk(topk) if topk != 0 or isinstance(topk, bool) else 0
+    if t is None and K == 0:
+        raise ValueError("render_select: nothing to select (no t and topk = 0)")
+    if t is not None:
+        check_median(t, P)
+        device = t.device
+    else:
+        device = torch.device(geomBuffer.device if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError(f"render_select: the MI355X rasterizer needs HIP device buffers, got {device.type}")
+    f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+    # every element is written
+    med, mid = (_empty((1, H, W), **f32), _empty((1, H, W), **i32)) if t is not None else (None, None)
+    ids, wts = (_empty((K, H, W), **i32), _empty((K, H, W), **f32)) if K else (None, None)
+    if _poison():  # (-1, _empty's integer poison, is a value the kernel writes)
+        for x in (mid, ids):
+            if x is not None:
+                x.fill_(-2)
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_select(P, int(num_rendered), W, H,
+                                           *_feature_buffers(geomBuffer, binningBuffer, imgBuffer), ptr(t), K,
+                                           ptr(med), ptr(mid), ptr(ids), ptr(wts), _stream_handle(device))
+    _lib.check(rc, "render_select")
+    return med, mid, ids, wts
+
+
+def render_median_backward(median_ids: torch.Tensor, dL_dmedian_map: torch.Tensor, P: int) -> torch.Tensor:
+    """The backward of ``render_select``'s median map (include/gsr.h gsr_render_median_backward): ``dL_dt`` [P], the
+    upstream gradient [1,H,W] scattered to each pixel's median Gaussian.  Float atomics in the hardware's order: not
+    bitwise reproducible."""
+    P = int(P)
+    device = median_ids.device
+    _require_device(median_ids, "median_ids")
+    if median_ids.dtype != torch.int32 or median_ids.dim() != 3 or median_ids.size(0) != 1:
+        raise RuntimeError(f"median_ids: expected an int32 [1,H,W] tensor, got {median_ids.dtype} "
+                           f"{tuple(median_ids.shape)}")
+    _, H, W = median_ids.shape
+    g = dL_dmedian_map
+    if tuple(g.shape) != (1, H, W) or g.dtype != torch.float32 or g.device != device:
+        raise RuntimeError(f"dL_dmedian_map: expected a float32 {(1, H, W)} tensor on {device}, got {g.dtype} "
+                           f"{tuple(g.shape)} on {g.device}")
+    f32 = dict(dtype=torch.float32, device=device)
+    if P == 0:
+        return torch.zeros((0,), **f32)
+    ins = _Inputs(device)
+    median_ids = median_ids.contiguous()
+    dL_dt = _empty((P,), **f32)  # every element is written
+    with torch.cuda.device(device):
+        rc = _lib.load().gsr_render_median_backward(P, int(W), int(H), median_ids.data_ptr(),
+                                                    ins.req(g, "dL_dmedian_map"), dL_dt.data_ptr(),
+                                                    _stream_handle(device))
+    _lib.check(rc, "render_median_backward")
+    return dL_dt
 
 
 def _scene_view(ins: _Inputs, *, means3D, dc, sh, degree, colors, opacities, scales, scale_modifier, rotations,

@@ -107,6 +107,9 @@ SIGNATURES = {
     "gsr_render_distortion": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
     "gsr_render_distortion_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_size_t, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, ALLOC_FN, _vp, _vp]),
+    "gsr_render_select": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, ctypes.c_size_t, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_render_select_max_k": (_i, []),
+    "gsr_render_median_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "gsr_camera_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _f,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ALLOC_FN, _vp, _vp, _vp, _vp, _vp]),
     "gsr_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),

@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libgsr.so")
-SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "contrib.hip", "features.hip", "distortion.hip", "alpha.hip", "backward.hip", "views.hip", "camera.hip", "knn.hip", "ssim.hip",
+SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "contrib.hip", "features.hip", "distortion.hip", "select.hip", "alpha.hip", "backward.hip", "views.hip", "camera.hip", "knn.hip", "ssim.hip",
            "adam.hip", "densify.hip", "ply.cpp"]
 # every header under csrc/ (tests/test_host.py checks that no file there is missing from the two lists)
 HEADERS = ["gsr_common.h", "kernels.h", "footprint.h", "host.h", "gauss_bwd_math.h", "camera.h", "camera_math.h"]
@@ -55,12 +55,13 @@ ABI_HEADERS = ("gsr.h", "gsr_knn.h", "gsr_ssim.h", "gsr_adam.h", "gsr_densify.h"
 # camera.hip (the camera backward) restates that math from the backward's own outputs and shares its SH
 # polynomial: the same flags, so its terms round as the dL/dmeans3D terms they mirror.
 _BACKWARD_FLAGS = ["-fno-slp-vectorize", "-ffp-contract=on"]
-# contrib.hip, features.hip and distortion.hip recompute the forward's alpha and transmittance: render.hip's flags,
+# contrib.hip, features.hip, distortion.hip and select.hip recompute the forward's alpha and transmittance: render.hip's flags,
 # so they round as there.
 FILE_FLAGS = {"render.hip": ["-fno-slp-vectorize"],
               "contrib.hip": ["-fno-slp-vectorize"],
               "features.hip": ["-fno-slp-vectorize"],
               "distortion.hip": ["-fno-slp-vectorize"],
+              "select.hip": ["-fno-slp-vectorize"],
               "backward.hip": _BACKWARD_FLAGS,
               "views.hip": _BACKWARD_FLAGS,
               "camera.hip": _BACKWARD_FLAGS,

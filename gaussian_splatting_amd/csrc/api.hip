@@ -1509,6 +1509,65 @@ int gsr_render_distortion_backward(int P, int R, int width, int height, const vo
     return GSR_OK;
 }
 
+// The selections ride the same walk and the same argument rules (features_args with C = 1); their outputs come in
+// two groups, each whole or absent.
+int gsr_render_select(int P, int R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                      const void* image_buffer, int binning_capacity, size_t binning_bytes, const float* t, int K,
+                      float* out_median, int* out_median_ids, int* out_topk_ids, float* out_topk_weights,
+                      void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    SelectArgs sa{};
+    bool walk = false;
+    if (int rc = features_args("render_select", P, 1, R, width, height, geom_buffer, binning_buffer, image_buffer,
+                               binning_capacity, binning_bytes, &sa.walk, &walk))
+        return rc;
+    if (K < 0 || K > kSelectMaxK) return fail(GSR_ERR_ARGUMENT, "render_select: K=%d (0 .. %d)", K, kSelectMaxK);
+    const bool median = out_median != nullptr;
+    if ((out_median_ids != nullptr) != median || (P > 0 && (t != nullptr) != median) || (P == 0 && t && !median))
+        return fail(GSR_ERR_ARGUMENT, "render_select: t, out_median and out_median_ids go together (all or none)");
+    if ((out_topk_ids != nullptr) != (K > 0) || (out_topk_weights != nullptr) != (K > 0))
+        return fail(GSR_ERR_ARGUMENT, "render_select: the top-K outputs are set exactly when K > 0 (K=%d)", K);
+    if (K == 0 && !median) return fail(GSR_ERR_ARGUMENT, "render_select: nothing to select (K = 0 and no median)");
+    if (!walk) {  // ids -1, floats 0
+        const size_t N = (size_t)width * height;
+        if (median) {
+            HIP_TRY(hipMemsetAsync(out_median, 0, sizeof(float) * N, stream), "render_select fill");
+            HIP_TRY(hipMemsetAsync(out_median_ids, 0xff, sizeof(int) * N, stream), "render_select fill");
+        }
+        if (K > 0) {
+            HIP_TRY(hipMemsetAsync(out_topk_ids, 0xff, sizeof(int) * N * K, stream), "render_select fill");
+            HIP_TRY(hipMemsetAsync(out_topk_weights, 0, sizeof(float) * N * K, stream), "render_select fill");
+        }
+        return GSR_OK;
+    }
+    sa.walk.features = t;
+    sa.K = K;
+    sa.out_median = out_median;
+    sa.out_median_ids = out_median_ids;
+    sa.out_topk_ids = out_topk_ids;
+    sa.out_topk_weights = out_topk_weights;
+    HIP_TRY(launch_select_fwd(sa, stream), "render_select");
+    return GSR_OK;
+}
+
+int gsr_render_select_max_k(void) { return gsr::kSelectMaxK; }
+
+int gsr_render_median_backward(int P, int width, int height, const int* median_ids, const float* dL_dout_median,
+                               float* dL_dt, void* stream_) {
+    using namespace gsr;
+    clear_error();
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0 || width <= 0 || height <= 0)
+        return fail(GSR_ERR_ARGUMENT, "render_median_backward: invalid sizes P=%d W=%d H=%d", P, width, height);
+    if (P == 0) return GSR_OK;
+    if (!median_ids || !dL_dout_median || !dL_dt)
+        return fail(GSR_ERR_ARGUMENT, "render_median_backward: null pointer");
+    HIP_TRY(launch_median_bwd(P, width, height, median_ids, dL_dout_median, dL_dt, stream), "render_median_backward");
+    return GSR_OK;
+}
+
 int gsr_debug_forward_state(int P, int width, int height, int R, int binning_capacity, size_t binning_bytes,
                             const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                             unsigned int* ranges, unsigned int* point_list, unsigned int* n_contrib, float* final_T,

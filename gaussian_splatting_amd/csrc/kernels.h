@@ -173,6 +173,19 @@ struct DistortionArgs {
                                   // writes them, the backward reads them
 };
 
+// Per-pixel selections (select.hip, include/gsr.h gsr_render_select / gsr_render_median_backward): the feature walk
+// with selection state in registers, one wave per tile.
+constexpr int kSelectMaxK = 8;    // pairs a lane can keep per pixel (4 slots x 2 registers each)
+struct SelectArgs {
+    // as the feature calls fill it, with C = 1: features = t [P] (read with out_median only); the outputs below
+    FeatureArgs walk;
+    int K;                        // top-K planes written, 0 .. kSelectMaxK
+    float* out_median;            // [H,W] t of the median contributor, or null (with out_median_ids: no median)
+    int* out_median_ids;          // [H,W] its Gaussian, -1 for a pixel without a contributor
+    int* out_topk_ids;            // [K,H,W], -1 beyond the pixel's contributor count (K > 0)
+    float* out_topk_weights;      // [K,H,W], 0 there
+};
+
 struct GaussBwdArgs {
     int P, D, M, W, H;
     const float* means3D;
@@ -512,6 +525,11 @@ hipError_t launch_features_bwd(const FeatureArgs& a, hipStream_t stream);
 // distortion.hip: one wave per tile; the backward's geometry variant is picked by DistortionArgs::walk.acc
 hipError_t launch_distortion_fwd(const DistortionArgs& a, hipStream_t stream);
 hipError_t launch_distortion_bwd(const DistortionArgs& a, hipStream_t stream);
+// select.hip: one wave per tile, the instantiation picked by SelectArgs::K and out_median; the median's scatter
+// backward, one thread per pixel (zeroes dL_dt [P] first)
+hipError_t launch_select_fwd(const SelectArgs& a, hipStream_t stream);
+hipError_t launch_median_bwd(int P, int W, int H, const int* median_ids, const float* dL_dmedian, float* dL_dt,
+                             hipStream_t stream);
 // Longest reachable prefix K4 sorts ("sort_prefix" option range; binning.hip kPrefixBuf holds twice it).
 constexpr uint32_t kSortPrefixMax = 1024;
 // backward.hip

@@ -14,7 +14,7 @@ import torch.nn as nn
 from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_RasterizeGaussiansCamera", "_RenderFeatures", "_RenderDistortion", "cpu_deep_copy_tuple"]
+           "_RasterizeGaussiansCamera", "_RenderFeatures", "_RenderDistortion", "_RenderMedian", "cpu_deep_copy_tuple"]
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -40,10 +40,11 @@ class GaussianRasterizationSettings(NamedTuple):
     antialiasing: bool
 
 
-def _rasterize_with_maps(args, features, distortion, kw):
-    """``rasterize_gaussians(..., features=F, distortion=t)`` (either or both): the render without the keywords, whose
-    node hands its buffers over, then the feature and / or distortion node behind it; ``feature_map`` then
-    ``distortion_map`` go after ``alpha`` and before the contribution statistics."""
+def _rasterize_with_maps(args, features, distortion, kw, median=None, topk=None):
+    """``rasterize_gaussians(..., features=F, distortion=t, median=t, topk=K)`` (any of them): the render without the
+    keywords, whose node hands its buffers over, then the feature, distortion and / or median node behind it (``topk=``
+    alone needs no node); ``feature_map``, ``distortion_map``, ``median_map, median_ids`` and ``topk_ids,
+    topk_weights`` go in that order after ``alpha`` and before the contribution statistics."""
     means3D, means2D = args[0], args[1]
     s = args[-1]
     scales, rotations, cov3D = args[-4], args[-3], args[-2]
@@ -52,7 +53,8 @@ def _rasterize_with_maps(args, features, distortion, kw):
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     has_cov = isinstance(cov3D, torch.Tensor) and cov3D.numel() != 0
     geom_in = (means3D, means2D, opacities, scales, rotations)
-    if has_cov and torch.is_grad_enabled() and any(
+    # (median= and topk= form no geometry gradient: nothing of theirs to refuse)
+    if has_cov and (features is not None or distortion is not None) and torch.is_grad_enabled() and any(
             isinstance(t, torch.Tensor) and t.requires_grad for t in geom_in + (cov3D,)):
         kws = " / ".join(k for k, v in (("features=", features), ("distortion=", distortion)) if v is not None)
         loss = "feature" if distortion is None else "distortion" if features is None else "feature / distortion"
@@ -64,6 +66,11 @@ def _rasterize_with_maps(args, features, distortion, kw):
         _C.check_features(features, means3D.size(0), device)
     if distortion is not None:
         _C.check_distortion(distortion, means3D.size(0), device)
+    if median is not None:
+        _C.check_median(median, means3D.size(0), device)
+    K = 0 if topk is None else _C.check_topk(topk)
+    if K and median is None:
+        _C._require_device(means3D, "means3D")
     _RasterizeGaussians._handover.value = True  # (read by the node's forward, which leaves its buffers there)
     try:
         outs = rasterize_gaussians(*args, **kw)
@@ -71,7 +78,8 @@ def _rasterize_with_maps(args, features, distortion, kw):
     finally:
         _RasterizeGaussians._handover.value = None
     if not isinstance(handed, tuple):
-        raise RuntimeError("rasterize_gaussians(features= / distortion=): the render did not hand over its buffers")
+        raise RuntimeError("rasterize_gaussians(features= / distortion= / median= / topk=): the render did not hand "
+                           "over its buffers")
     empty = means3D.new_empty(0)
     tail = (means3D, means2D, opacities, empty if has_cov else scales, empty if has_cov else rotations, outs[1],
             *handed[:3], s, handed[3])  # both nodes receive the buffers of the one render
@@ -80,6 +88,11 @@ def _rasterize_with_maps(args, features, distortion, kw):
         maps += (_RenderFeatures.apply(features, *tail),)
     if distortion is not None:
         maps += (_RenderDistortion.apply(distortion, *tail),)
+    if median is not None:  # (one launch serves both keywords)
+        maps += _RenderMedian.apply(median, *handed[:3], s, handed[3], K)
+    elif K:
+        maps += _C.render_select(*handed, means3D.size(0), s.image_height, s.image_width, topk=K,
+                                 device=means3D.device)[2:]
     n = 4 if kw.get("return_alpha") else 3
     return outs[:n] + maps + outs[n:]
 
@@ -177,8 +190,33 @@ class _RenderDistortion(torch.autograd.Function):
         return _map_node_grads(ctx, s, dL_dt, block, means3D, opacities, scales, rotations)
 
 
+class _RenderMedian(torch.autograd.Function):
+    """The median node behind the rasterizer node: forward = ``_C.render_select`` over the rasterizer node's buffers
+    (with the top-K planes too when ``topk=`` came with ``median=``: one launch), backward =
+    ``_C.render_median_backward``.  Inputs ``(t, geom, binning, img, raster_settings, num_rendered, K)``; ``t`` is the
+    only differentiable one -- the median is piecewise constant in the blend weights, so the geometry receives a
+    gradient only through whatever torch built ``t`` from.  Outputs ``(median_map, median_ids[, topk_ids,
+    topk_weights])``, all but the first non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, t, geom, binning, img, s, num_rendered, K):
+        med, ids, tk_ids, tk_w = _C.render_select(geom, binning, img, num_rendered, t.size(0), s.image_height,
+                                                  s.image_width, t=t, topk=K)
+        ctx.P = t.size(0)
+        ctx.save_for_backward(ids)
+        rest = (ids,) if not K else (ids, tk_ids, tk_w)
+        ctx.mark_non_differentiable(*rest)
+        return (med,) + rest
+
+    @staticmethod
+    def backward(ctx, grad_med, *_rest):
+        (ids,) = ctx.saved_tensors
+        dL_dt = _C.render_median_backward(ids, grad_med.contiguous(), ctx.P) if ctx.needs_input_grad[0] else None
+        return (dL_dt,) + (None,) * 6
+
+
 def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib=False, contrib_weight=None,
-                        features=None, distortion=None):
+                        features=None, distortion=None, median=None, topk=None):
     """``rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
     raster_settings)`` (vendored, :24-46), or the 3DGS-accel form with ``dc`` before ``sh``.
 
@@ -217,13 +255,31 @@ def rasterize_gaussians(*args, return_alpha=False, absgrad=False, return_contrib
     included) and, through an autograd node of its own (``_RenderDistortion``), to the geometry exactly as
     ``features=``, with the same limits: the kernel's geometry part does not reach the camera tensors or
     ``means2D.absgrad``, and ``cov3D_precomp`` with a geometry input that requires grad is refused.  Without the
-    keyword nothing more is launched or allocated."""
+    keyword nothing more is launched or allocated.  The distortion loss and the median depth below are meant to be
+    used from one render.
+
+    ``median=t`` (an extension, the median depth of 2DGS / GOF / RaDe-GS / PGSR): ``t`` as for ``distortion=``.  Two
+    more outputs after ``distortion_map``: ``median_map`` [1,H,W], per pixel ``t`` of its median contributor -- the
+    last one blended while the transmittance is above one half (the one that takes it to one half or below, or the
+    pixel's last contributor) -- and ``median_ids`` [1,H,W] int32, that contributor's Gaussian index; a pixel without
+    a contributor holds 0.0 and -1 (include/gsr.h gsr_render_select).  ``median_map`` is differentiable with respect
+    to ``t`` ONLY: it is a copy of ``t``, piecewise constant in the blend weights, so there is no geometry gradient
+    through the kernel (2DGS forms none either); the gradient reaches ``means3D`` and the camera tensors through
+    whatever torch built ``t`` from (autograd node ``_RenderMedian``).  ``median_ids`` is not differentiable.
+    ``cov3D_precomp`` with geometry inputs that require grad is accepted.
+
+    ``topk=K`` (an extension; ``1 <= K <= _C.select_max_k()``, 8): two more outputs after the median's, ``topk_ids``
+    [K,H,W] int32 and ``topk_weights`` [K,H,W] float32: per pixel the K contributors of largest blend weight in
+    descending weight, the earlier in blend order first on equal weights; ranks beyond the pixel's contributor count
+    hold -1 and 0.0.  For picking, id buffers, lifting 2D masks or labels onto Gaussians, per-pixel debugging.  Not
+    differentiable: ``features=`` is the differentiable blend.  With ``median=`` both come from one launch.  Without
+    the keywords nothing more is launched or allocated."""
     if len(args) not in (9, 10):
         raise TypeError(f"rasterize_gaussians(): expected 9 or 10 arguments, got {len(args)}")
-    if features is not None or distortion is not None:
+    if features is not None or distortion is not None or median is not None or topk is not None:
         return _rasterize_with_maps(args, features, distortion,
                                     dict(return_alpha=return_alpha, absgrad=absgrad, return_contrib=return_contrib,
-                                         contrib_weight=contrib_weight))
+                                         contrib_weight=contrib_weight), median=median, topk=topk)
     _RasterizeGaussians._return_alpha.value = bool(return_alpha)  # (read and cleared by the node's forward)
     _RasterizeGaussians._absgrad.value = bool(absgrad)            # (likewise)
     if contrib_weight is not None and not return_contrib:
@@ -258,7 +314,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     _return_alpha = threading.local()  # set by rasterize_gaussians(..., return_alpha=True) for its one call
     _absgrad = threading.local()       # set by rasterize_gaussians(..., absgrad=True) for its one call
     _contrib = threading.local()       # set by rasterize_gaussians(..., return_contrib=True): (contrib_weight,)
-    _handover = threading.local()      # True for a call with features= / distortion=; the forward leaves its buffers
+    _handover = threading.local()      # True for a call with a map keyword: the forward leaves its buffers
 
     @staticmethod
     def _absgrad_kw(ctx):
@@ -325,7 +381,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(*saved, *(() if dc is None else (dc,)))
         outs = (color, radii, invdepths, alpha) if with_alpha else (color, radii, invdepths)
         if getattr(_RasterizeGaussians._handover, "value", None) is True:
-            # features= / distortion=: the buffers saved above are handed to the nodes behind this one
+            # features= / distortion= / median= / topk=: the buffers saved above are handed to the nodes behind this one
             # (rasterize_gaussians), nothing else
             _RasterizeGaussians._handover.value = (geom, binning, img, num_rendered)
         if contrib is None:
@@ -430,7 +486,7 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, dc=None, return_alpha=False, absgrad=False, return_contrib=False,
-                contrib_weight=None, features=None, distortion=None):
+                contrib_weight=None, features=None, distortion=None, median=None, topk=None):
         """Same checks as the reference (:242-261).  ``dc=`` (keyword) selects the 3DGS-accel separate-SH
         input: ``dc`` = ``_features_dc`` [P,1,3] and ``shs`` = ``_features_rest`` [P,M,3]
         (gaussian_renderer/__init__.py:115-125).  ``return_alpha=True`` returns ``(color, radii, invdepths,
@@ -439,7 +495,9 @@ class GaussianRasterizer(nn.Module):
         ``return_contrib=True`` [+ ``contrib_weight=``]: the per-Gaussian contribution statistics [P,4] as the last
         output (``rasterize_gaussians``).  ``features=`` [P,C]: one more differentiable output ``feature_map``
         [C,H,W], after ``alpha`` and before the statistics; ``distortion=`` [P]: one more differentiable output
-        ``distortion_map`` [1,H,W], after ``feature_map`` (``rasterize_gaussians``)."""
+        ``distortion_map`` [1,H,W], after ``feature_map``; ``median=`` [P]: ``median_map`` [1,H,W] (differentiable
+        with respect to ``median`` only) and ``median_ids`` [1,H,W] int32 after it; ``topk=K``: ``topk_ids`` and
+        ``topk_weights`` [K,H,W] after those, not differentiable (``rasterize_gaussians``)."""
         s = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide exactly one of either SHs or precomputed colors!")
@@ -459,6 +517,10 @@ class GaussianRasterizer(nn.Module):
             contrib_kw = dict(contrib_kw, features=features)
         if distortion is not None:
             contrib_kw = dict(contrib_kw, distortion=distortion)
+        if median is not None:
+            contrib_kw = dict(contrib_kw, median=median)
+        if topk is not None:
+            contrib_kw = dict(contrib_kw, topk=topk)
         if dc is None:
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, s, return_alpha=return_alpha, absgrad=absgrad, **contrib_kw)

@@ -348,6 +348,47 @@ int gsr_render_distortion_backward(int P, int R, int width, int height, const vo
                                    const float* campos, float tan_fovx, float tan_fovy, int antialiasing,
                                    const int* radii, gsr_alloc_fn scratch_alloc, void* scratch_ctx, void* stream);
 
+/* Per-pixel selections from the blend weights: WHICH Gaussian a pixel "is".  Every other per-pixel output is a sum
+ * over the weights; these are arg-selects over them, which no feature map and no autograd graph can give.  For a
+ * pixel let 1..n be its contributing entries in the forward's list order -- the (pixel, Gaussian) pairs of
+ * gsr_contrib_stats: blended, before termination, below the pixel's n_contrib -- T_i the transmittance BEFORE entry
+ * i is blended (T_1 = 1) and w_i = alpha_i T_i.
+ *   Median contributor m: the LAST contributor with T_m > 0.5 (2DGS's rule, `if (T > 0.5) { median_depth = depth;
+ *     median_contributor = ...; }` evaluated before T is updated): the contributor that takes T from above one half
+ *     to at most one half, or the pixel's last contributor when T never gets there.  median_ids[pix] is m's Gaussian
+ *     index (int32) and median[pix] = t[m], a COPY of the caller's per-Gaussian scalar t [P] (float32; view depth for
+ *     the median depth, conventions as gsr_render_distortion's t).  A pixel with no contributor: id -1, value 0.0.
+ *   Top-K, 1 <= K <= gsr_render_select_max_k() (8): the K contributors of largest w in descending w; on equal w the
+ *     earlier one in list order ranks first (a later entry displaces only on strict >).  topk_ids [K,H,W] int32 and
+ *     topk_weights [K,H,W] float32; ranks beyond the pixel's contributor count hold id -1 and weight 0.0.
+ * No background term.  Each pixel is written once by the wave that owns it, nothing is added atomically: all four
+ * outputs are bitwise reproducible, and the same bits after a half-tile, a whole-tile ("fwd_quads" 4) or a
+ * no_backward forward and for copies of the buffers.  The expected depth invdepth / alpha blurs across depth
+ * discontinuities; the median does not, and is meant to be used beside the distortion map of the same render.
+ *
+ * gsr_render_select: from the three buffers of a finished forward (as gsr_render_features takes them, under the same
+ *   conditions; argument rules and error codes are gsr_render_features' with C = 1) in ONE pass for both selections.
+ *   t, out_median and out_median_ids are all set or all NULL (no median); K in 0 .. max and out_topk_ids,
+ *   out_topk_weights set exactly when K > 0; K == 0 without the median is GSR_ERR_ARGUMENT.  Every element of the
+ *   outputs given is written.  P == 0 or R == 0 fills ids with -1 and floats with 0 (the buffers, and with P == 0
+ *   t, may then be NULL).  Read-only on the buffers and repeatable; a backward of the colour before or after it is
+ *   unaffected.
+ * gsr_render_select_max_k: the largest K this build supports.
+ * gsr_render_median_backward: dL_dt[g] = sum over the pixels with median_ids[pix] == g of dL_dout_median[pix]
+ *   ([H,W]); every element of dL_dt ([P]) is written (zeroed, then added into with float atomics in the hardware's
+ *   order: NOT bitwise reproducible); ids outside 0 .. P-1 are skipped.  The median is piecewise constant in the
+ *   blend weights, so there is no geometry gradient (2DGS forms none either): t is its only differentiable input, and
+ *   the gradient reaches the geometry through whatever t was computed from.  The ids and the top-K outputs are not
+ *   differentiable (gsr_render_features blends differentiably).  P == 0 does nothing. */
+int gsr_render_select(int P, int R, int width, int height, const void* geom_buffer, const void* binning_buffer,
+                      const void* image_buffer, int binning_capacity, size_t binning_bytes,
+                      const float* t /* [P] or NULL */, int K, float* out_median /* [H,W] or NULL */,
+                      int* out_median_ids /* [H,W] or NULL */, int* out_topk_ids /* [K,H,W] or NULL */,
+                      float* out_topk_weights /* [K,H,W] or NULL */, void* stream);
+int gsr_render_select_max_k(void);
+int gsr_render_median_backward(int P, int width, int height, const int* median_ids /* [H,W] */,
+                               const float* dL_dout_median /* [H,W] */, float* dL_dt /* [P] */, void* stream);
+
 /* Multi-GPU view exchange (gaussian_splatting_amd/distributed.py
  * ViewExchange).  The reference trains on one GPU; sharding views over N ranks needs the
  * N views' parameter gradients summed on every rank.  Instead of all-reducing the 59-float
