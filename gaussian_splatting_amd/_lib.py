@@ -16,7 +16,8 @@ DEFAULT_LIB = os.path.join(_PKG, "lib", "libgsr.so")
 LIB_PATH = os.environ.get("GSR_LIBRARY", DEFAULT_LIB)
 INCLUDE_DIR = os.path.join(os.path.dirname(_PKG), "include")
 HEADER_PATH = os.path.join(INCLUDE_DIR, "gsr.h")
-HEADERS = [os.path.join(INCLUDE_DIR, h) for h in ("gsr.h", "gsr_knn.h", "gsr_ssim.h", "gsr_adam.h", "gsr_densify.h", "gsr_ply.h")]
+HEADERS = [os.path.join(INCLUDE_DIR, h) for h in ("gsr.h", "gsr_knn.h", "gsr_ssim.h", "gsr_adam.h", "gsr_densify.h", "gsr_mcmc.h",
+                                                      "gsr_ply.h")]
 
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
@@ -38,6 +39,13 @@ class DensifyGroup(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_exp_avg", ctypes.c_void_p),
                 ("src_exp_avg_sq", ctypes.c_void_p), ("dst_exp_avg", ctypes.c_void_p),
                 ("dst_exp_avg_sq", ctypes.c_void_p), ("width", ctypes.c_int), ("role", ctypes.c_int)]
+
+
+class McmcGroup(ctypes.Structure):
+    """gsr_mcmc_group (include/gsr_mcmc.h)."""
+
+    _fields_ = [("data", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("width", ctypes.c_int), ("role", ctypes.c_int)]
 
 
 class DensifyParams(ctypes.Structure):
@@ -159,6 +167,10 @@ SIGNATURES = {
                               ctypes.POINTER(ctypes.c_longlong), _vp]),
     "gsr_densify_apply": (_i, [_i, _vp, ctypes.POINTER(DensifyGroup), _i, _vp, _vp, _vp, _vp,
                                ctypes.POINTER(DensifyParams), _vp]),
+    "gsr_mcmc_noise": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _f, _vp]),
+    "gsr_mcmc_scratch_bytes": (ctypes.c_ulonglong, [_i]),
+    "gsr_mcmc_relocation": (_i, [_i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_mcmc_apply": (_i, [_i, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(McmcGroup), _i, _vp]),
     "gsr_ply_open": (_i, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
     "gsr_ply_close": (None, [_vp]),
     "gsr_ply_vertex_count": (ctypes.c_longlong, [_vp]),

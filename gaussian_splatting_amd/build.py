@@ -21,7 +21,7 @@ OBJ = os.path.join(PKG, "build")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libgsr.so")
 SOURCES = ["api.hip", "preprocess.hip", "binning.hip", "render.hip", "contrib.hip", "features.hip", "distortion.hip", "select.hip", "alpha.hip", "backward.hip", "views.hip", "camera.hip", "knn.hip", "ssim.hip",
-           "adam.hip", "densify.hip", "ply.cpp"]
+           "adam.hip", "densify.hip", "mcmc.hip", "ply.cpp"]
 # every header under csrc/ (tests/test_host.py checks that no file there is missing from the two lists)
 HEADERS = ["gsr_common.h", "kernels.h", "footprint.h", "host.h", "gauss_bwd_math.h", "camera.h", "camera_math.h"]
 ARCH = os.environ.get("GSR_OFFLOAD_ARCH", "gfx950")
@@ -30,7 +30,7 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-W
             "-I", os.path.join(ROOT, "include"), "-I", CSRC]
 
 
-ABI_HEADERS = ("gsr.h", "gsr_knn.h", "gsr_ssim.h", "gsr_adam.h", "gsr_densify.h", "gsr_ply.h")
+ABI_HEADERS = ("gsr.h", "gsr_knn.h", "gsr_ssim.h", "gsr_adam.h", "gsr_densify.h", "gsr_mcmc.h", "gsr_ply.h")
 
 
 # Per-file flags.  The SLP vectorizer packs adjacent fp32 ops into v_pk_*_f32 plus
