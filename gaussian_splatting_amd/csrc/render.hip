@@ -13,8 +13,8 @@
 //    blend checkpoint;
 //  * list entries are staged 64 at a time (one per lane) into LDS as 48-byte
 //    splat records; while loading, each entry's alpha >= 1/255 footprint (its
-//    box, then the ellipse itself) is tested against the four quadrants (4-bit
-//    mask, conservative);
+//    box, then the ellipse itself) is tested against the wave's own quadrants
+//    (one mask bit each, conservative: footprint.h);
 //  * the wave walks only entries whose mask is non-zero (scalar bit scan of a
 //    ballot) and, per entry, runs only the slots whose bit is set -- uniform
 //    branches, no vector work for culled quadrants;
@@ -93,7 +93,7 @@ __device__ __forceinline__ float splat_alpha(float p2, float opacity, float& G) 
 // lane of this slot blend this splat" and "is any pixel of this slot still live".
 // SGPR budget of the forward: at .sgpr_count 82-96 the hardware admits 7 one-wave workgroups per
 // SIMD, at <= 80 eight (MI355X_MICROARCH.md "Residency"); the VGPRs (61) allow eight.
-// (r4b: render_fwd 199-200 -> 195-197 us; 8 SGPRs spill to VGPR lanes, prologue only)
+// (r4b: render_fwd 199-200 -> 195-197 us; 4 SGPRs spill to VGPR lanes, prologue only)
 #define GSR_FWD_OCCUPANCY __attribute__((amdgpu_num_sgpr(80)))
 // One wave per PART of a tile: NQ = 4 quadrants (the whole 16x16 tile) or NQ = 2 (its top or
 // bottom half).  Each lane owns one pixel in each of the part's NQ quadrants ("slots").  With
@@ -131,7 +131,6 @@ __device__ __forceinline__ FwdLds& fwd_lds() {
 template <int NQ, bool CENSUS>
 __device__ __forceinline__ void render_fwd_tile(const RenderFwdArgs& a, const uint32_t tile, const int part) {
   {
-    constexpr uint32_t kPartMask = (1u << NQ) - 1u;
     constexpr int NPART = 4 / NQ;
     const uint32_t tiles = a.gx * a.gy;
     const int qbase = part * NQ;  // first quadrant of this part
@@ -185,12 +184,13 @@ __device__ __forceinline__ void render_fwd_tile(const RenderFwdArgs& a, const ui
             const float4 v0 = rec[0], v1 = rec[1], v2 = rec[2];
             s_xy[lane] = make_float4(v0.x, v0.y, v1.y, v1.z);
             s_col[lane] = v2;
-            // this part's quadrants only; the backward (which visits only staged entries) gets every
-            // part's blend bits OR-ed into the entry K4 wrote with clear mask bits.  A part that stopped
+            // this part's quadrants only (bit k: quadrant qbase + k, the first of them at the origin passed:
+            // a scalar add, so one copy of the test serves every part); the backward (which visits only
+            // staged entries) gets every part's blend bits OR-ed into the entry K4 wrote with clear mask bits.  A part that stopped
             // before an entry leaves its bits clear there: its pixels all ended earlier, so the
             // backward has retired those slots by then (slot limits from n_contrib).
-            qm = quad_bits_exact(v0, v1, v2, tile_x0, tile_y0, kPartMask << qbase);
-            s_cq[lane] = stage_conic(v0, v1, qm >> qbase);
+            qm = quad_bits<NQ>(v0, v1, v2, tile_x0 + (qbase & 1) * 8, tile_y0 + (qbase >> 1) * 8);
+            s_cq[lane] = stage_conic(v0, v1, qm);
         }
         if (b0 + kBatch + lane < ns) ent_next = a.gid_sorted[range.x + b0 + kBatch + lane];
         unit_sync();
@@ -214,7 +214,7 @@ __device__ __forceinline__ void render_fwd_tile(const RenderFwdArgs& a, const ui
                 ck[(4 * 4 + q) * 64] = D[k];
             }
         }
-        unsigned long long todo = __ballot((qm >> qbase) & kPartMask);
+        unsigned long long todo = __ballot(qm);
         // bit j of blend[k]: some pixel of quadrant k blended entry j (one 64-bit mask per quadrant in
         // SGPRs; under the 80-SGPR budget those spill to VGPR lanes)
         unsigned long long blend[NQ];
